@@ -5,11 +5,16 @@ A "step" = one pass of the hot path (fused LIS score + hard top-k + gather, `vse
 batch of synthetic visual tokens H[B, N, D] that is already resident in HBM.  Workload = BASELINE.json
 configs[1]: Qwen2.5-VL-7B geometry (D=3584, Hd=1792), N_vis=2304 (1344x1344), 20 % retain (k=460).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--images B] [--budget r]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--images B] [--budget r] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Multi-GPU: images are independent units -> each rank processes its own B images,
 no data-path collective ("weak" scaling); only the barrier and the max-over-ranks of the time use RCCL.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else:
+the instrumented per-kernel pass and its roofline, the parity check against the fp64 oracle,
+the training / single-sweep / batch-1 / attention / config / LLM-prefill legs and the CPU baseline (each leg can
+still be dropped with its --no-* option).  --dump-outputs DIR writes what the last timed step computed as .npy files.
 
 Prints ONE JSON line on rank 0 (see the keys at the bottom).
 """
@@ -162,6 +167,28 @@ def pmc_traffic(kernel, b):
         return None
 
 
+DUMP_SEED = 20240601
+DUMP_BUDGET = {"scores": 8 << 20, "indices": 8 << 20, "selected_tokens": 40 << 20}     # bytes per array: 56 MB + row lists < 64 MB
+
+
+def dump_outputs(dirname, out, idx, scores):
+    """What the timed path hands its caller, as float32 / float64 .npy files under `dirname`: scores [B, N], kept indices
+    [B, k] and the gathered tokens [B, k, D].  An array larger than its DUMP_BUDGET share is cut to a fixed, seeded sample
+    of its rows (flattened to [rows, last dim]); `<name>_rows.npy` then lists the rows that were kept.  Identical
+    arguments give identical inputs, so two builds can be compared file by file."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t, dtype in (("scores", scores, np.float32), ("indices", idx, np.float64), ("selected_tokens", out, np.float32)):
+        rows, cols = t.numel() // t.shape[-1], t.shape[-1]
+        keep = max(1, DUMP_BUDGET[name] // (cols * np.dtype(dtype).itemsize))
+        if rows > keep:
+            sel = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, keep, replace=False))
+            np.save(os.path.join(dirname, f"{name}_rows.npy"), sel.astype(np.float64))
+            t = t.reshape(rows, cols)[torch.from_numpy(sel).to(t.device)]
+        a = t.cpu() if t.dtype == torch.int64 else t.float().cpu()
+        np.save(os.path.join(dirname, f"{name}.npy"), a.numpy().astype(dtype))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -176,7 +203,15 @@ def main():
     ap.add_argument("--no-single-sweep", action="store_true", help="skip the producer-side column-sum leg (SURVEY 8f N2)")
     ap.add_argument("--no-batch1", action="store_true", help="skip the one-image-per-call leg")
     ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE config sweep / config-5 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the instrumented per-kernel pass (roofline), the oracle parity check, every leg not "
+                         "switched off by a --no-* option and the CPU baseline; a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (scores, indices, a seeded sample of the kept tokens) "
+                         "as DIR/<name>.npy, rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher (what the reference's scripts do with torchrun /
@@ -199,7 +234,7 @@ def main():
 
     # what the collective library itself saw (world > 1): the line's n_gpus is otherwise only the launcher's WORLD_SIZE
     rccl = None
-    if dist:
+    if dist and args.full:
         ones = torch.ones(1, device="cuda")
         dist.all_reduce(ones)
         props = torch.cuda.get_device_properties(local_rank)
@@ -235,6 +270,33 @@ def main():
     if dist:
         dist.barrier()
         torch.cuda.synchronize()
+    elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device="cuda")
+    if dist:
+        dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
+    elapsed = float(elapsed.item())
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * b * n / (elapsed / args.steps)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, idx, scores)
+    res = {
+        "metric": "vision_tokens_scored_selected_per_sec", "value": value, "unit": "tokens/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "accumulate": "f32",
+        "data": "synthetic",
+        "config": {"workload": "Qwen2.5-VL-7B LIS score + hard top-k + gather (vsel_lis_select), N_vis=2304, D=3584, "
+                               "Hd=1792, 20% retain (k=460)" if args.budget == 0.2 else
+                               f"Qwen2.5-VL-7B LIS select, N_vis=2304, D=3584, Hd=1792, budget={args.budget} (k={k})",
+                   "images_per_step_per_gpu": b, "n_vis": n, "d": d, "hd": hd, "k": k, "budget": args.budget,
+                   "sharding": f"{world} independent replicas, one process per GPU, no data-path collective"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # instrumented repeat of the same K steps: libvsel records a HIP event after every kernel on the launch
     # stream (per-kernel durations for the roofline).  The events themselves cost a few us per kernel boundary,
     # so `value` comes from the un-instrumented region above; both step times are reported.
@@ -245,12 +307,6 @@ def main():
     torch.cuda.synchronize()
     tp1 = time.perf_counter()
     prof = _native.profile_stop()
-    elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device="cuda")
-    if dist:
-        dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
-    elapsed = float(elapsed.item())
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * b * n / (elapsed / args.steps)
 
     # ---- parity gate on the timed data (one image, fp64 collapsed oracle on the host) ----------------
     parity = None
@@ -323,19 +379,10 @@ def main():
                     "note": "no per-kernel timing available: SURVEY 8(d) path bytes / step time"}
     path = {"algorithmic_bytes_per_step": path_bytes, "achieved_GBps": path_gbs, "frac_of_8TBps": path_gbs / HBM_PEAK_GBS}
 
-    res = {
-        "metric": "vision_tokens_scored_selected_per_sec", "value": value, "unit": "tokens/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "accumulate": "f32",
-        "data": "synthetic",
-        "config": {"workload": "Qwen2.5-VL-7B LIS score + hard top-k + gather (vsel_lis_select), N_vis=2304, D=3584, "
-                               "Hd=1792, 20% retain (k=460)" if args.budget == 0.2 else
-                               f"Qwen2.5-VL-7B LIS select, N_vis=2304, D=3584, Hd=1792, budget={args.budget} (k={k})",
-                   "images_per_step_per_gpu": b, "n_vis": n, "d": d, "hd": hd, "k": k, "budget": args.budget,
-                   "sharding": f"{world} independent replicas, one process per GPU, no data-path collective"},
+    res.update({
         "ms_per_step_instrumented": (tp1 - tp0) / args.steps * 1e3,
         "roofline": roofline, "roofline_path": path, "kernels": kern, "parity": parity,
-    }
+    })
 
     if rccl is not None:
         res["rccl"] = rccl

@@ -23,8 +23,10 @@ What is executed from the reference (paths under /root/reference):
         merger), and LLaVAOneVision1_5_Model_Selector.forward (splice :259-276, 1-D position_ids / cache_position /
         attention_mask selection :308-314) on a recording language model
 
-Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [--ov-only | --bf16-only]
+Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [--ov-only | --bf16-only | --dropin-imports]
         (--bf16-only: the same LIS cases with the reference modules and tokens in bfloat16 -> lisbf16_*.npz)
+        (--dropin-imports: which `compression_method.*` / `token_compression.*` names the reference's caller scripts import,
+         read with `ast`, nothing executed -> dropin_caller_imports.json for tests/test_dropin_callers_cpu.py)
 """
 import importlib.machinery
 import os
@@ -511,7 +513,31 @@ def gen_ov_splice_case(name, ov, n_visual, n_pre, n_post, k, seed, d_llm=32, wit
     print(f"ov splice {name}: L={L} -> L'={seen['inputs_embeds'].shape[1]}")
 
 
+def gen_dropin_imports():
+    """(line, module, [names]) of every absolute `compression_method.*` / `token_compression.*` from-import of the caller
+    scripts tests/test_dropin_callers_cpu.py checks the drop-in packages against."""
+    import ast
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_dropin_callers_cpu import CALLERS
+    out = {}
+    for caller, _ in CALLERS:
+        rows = []
+        for node in ast.walk(ast.parse(open(os.path.join(REF, caller)).read())):
+            if (isinstance(node, ast.ImportFrom) and node.level == 0 and node.module
+                    and node.module.split(".")[0] in ("compression_method", "token_compression")):
+                rows.append([node.lineno, node.module, [a.name for a in node.names]])
+        out[caller] = sorted(rows)
+    with open(os.path.join(HERE, "dropin_caller_imports.json"), "w") as f:                 # one import per line
+        f.write("{\n" + ",\n".join(f"{json.dumps(c)}: [\n  " + ",\n  ".join(json.dumps(r) for r in rows) + "]"
+                                      for c, rows in out.items()) + "\n}\n")
+    print(f"dropin imports: {sum(len(v) for v in out.values())} statements from {len(out)} callers")
+
+
 def main():
+    if "--dropin-imports" in sys.argv:
+        gen_dropin_imports()
+        return
     if "--ov-only" in sys.argv:
         ov, OVScorer = load_ov()
         gen_ov_lis_case("8x81", ov, OVScorer, 256, 128, [[1, 9, 9]] * 8, 41)

@@ -23,7 +23,8 @@ def _run_bench(*args, timeout=900):
 
 
 def test_bench_line_one_gpu_small():
-    res = _run_bench("--steps", "3", "--warmup", "1", "--images", "8", "--no-cpu-baseline", "--no-attn", "--no-llm", "--no-train")
+    res = _run_bench("--full", "--steps", "3", "--warmup", "1", "--images", "8", "--no-cpu-baseline", "--no-attn", "--no-llm",
+                     "--no-train")
     assert res["metric"] == "vision_tokens_scored_selected_per_sec" and res["n_gpus"] == 1 and res["steps"] == 3
     rf = res["roofline"]
     # frac is ALWAYS a number (round 5's driver run died here on None: the clock had named a helper kernel without a byte model); at 8
@@ -37,13 +38,31 @@ def test_bench_line_one_gpu_small():
     assert p["idx_equal_fp64_oracle"] and p["idx_equal_own_scores"] and p["gather_exact"]
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run carries the headline keys only; --dump-outputs writes the last timed step's outputs, the same on a rerun."""
+    import numpy as np
+    args = ("--steps", "2", "--warmup", "1", "--images", "4")
+    res = _run_bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    assert res["metric"] == "vision_tokens_scored_selected_per_sec" and res["unit"] == "tokens/s" and res["dtype"] == "bf16"
+    assert res["higher_is_better"] is True and res["steps"] == 2 and res["ms_per_step"] > 0 and res["value"] > 0
+    assert not {"roofline", "kernels", "parity", "train_step", "cpu_baseline"} & set(res)
+    _run_bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    k = res["config"]["k"]
+    assert np.load(tmp_path / "a" / "scores.npy").shape == (4, 2304)
+    idx = np.load(tmp_path / "a" / "indices.npy")
+    assert idx.shape == (4, k) and idx.dtype == np.float64 and np.all(np.diff(idx, axis=1) > 0)
+    assert np.load(tmp_path / "a" / "selected_tokens.npy").shape == (4, k, 3584)
+    for f in ("scores.npy", "indices.npy", "selected_tokens.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+
+
 def test_bench_self_spawns_one_rank_per_gpu_over_rccl():
     n = torch.cuda.device_count()
     if n < 2:
         pytest.skip("one GPU visible: the multi-rank RCCL path needs >= 2")
     n = 2 if n < 4 else 4
-    res = _run_bench("--gpus", str(n), "--steps", "3", "--warmup", "1", "--images", "8", "--no-cpu-baseline", "--no-attn",
-                     "--no-llm")
+    res = _run_bench("--full", "--gpus", str(n), "--steps", "3", "--warmup", "1", "--images", "8", "--no-cpu-baseline",
+                     "--no-attn", "--no-llm")
     assert res["n_gpus"] == n and res["scaling"] == "weak" and res["value"] > 0
     tr = res["train_step"]["packed_16x64_tokens"]
     assert res["train_step"]["world"] == n and tr["allreduce_busbw_GBps"] is not None and tr["allreduce_busbw_GBps"] > 0

@@ -1,15 +1,15 @@
 """The drop-in import surface, checked against the reference's own callers.
 
-Build container only: needs /root/reference (skipped on the GPU box).  For each script of the reference that imports
-`compression_method.*` / `token_compression.*`, the import statements are extracted with `ast` and executed UNCHANGED with
-`visionselector_amd/dropin` ahead of the reference's package root on sys.path:
+For each script of the reference that imports `compression_method.*` / `token_compression.*`, the names it imports are
+stored in tests/golden/dropin_caller_imports.json (recorded with `ast` by `tests/golden/make_golden.py --dropin-imports`).
+Those import statements are executed UNCHANGED with `visionselector_amd/dropin` ahead of a package root that stands in
+for the reference's (built per test under tmp_path: the baseline modules the callers import, as stubs of those names):
 
   * every selector-path name (TransformerScorer, topk, *_forward_selector, *_Selector classes, replace_*) must resolve to
     this library;
   * every baseline module the same scripts import unconditionally (`token_compression.visionzip_official`,
-    `.dynamic_model`, ...) must still be FOUND in the reference tree behind ours (dropin packages are namespace
-    portions); a baseline that then fails inside the reference's own code under this image's transformers is the
-    reference's incompatibility, not a shadowing defect, and is accepted only when raised from outside this repo."""
+    `.dynamic_model`, ...) must still be FOUND in the package root behind ours (dropin packages are namespace
+    portions); a baseline that fails to import is accepted only when it raised from outside this repo."""
 import json
 import os
 import subprocess
@@ -18,10 +18,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 DROPIN = os.path.join(ROOT, "visionselector_amd", "dropin")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference tree (build container only)")
+IMPORTS = os.path.join(ROOT, "tests", "golden", "dropin_caller_imports.json")
 
 # (caller script, package root the reference's launch scripts put on PYTHONPATH for it)
 CALLERS = [
@@ -38,21 +36,90 @@ OURS = {"compression_method.selector_scorer", "compression_method.selector_model
         "compression_method.monkeypatch", "token_compression.selector_scorer", "token_compression.selector_model",
         "token_compression.monkeypatch"}
 
+# Stand-in for the LLaVA-OV-1.5 model code the llava-ov-15 root vendors (`llavaonevision1_5`): the three base classes the
+# selector classes subclass, and a config that carries the tower's sizes
+OV_MODELING = """import torch
 
-def _probe(caller, root):
+
+class RiceTransformerPretrainedModel(torch.nn.Module):
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        self.blocks = torch.nn.ModuleList(torch.nn.Linear(config.embed_dim, config.embed_dim) for _ in range(config.depth))
+
+
+class LLaVAOneVision1_5_Model(torch.nn.Module):
+    pass
+
+
+class LLaVAOneVision1_5_ForConditionalGeneration(torch.nn.Module):
+    pass
+"""
+OV_CONFIG = """class RiceConfig:
+    def __init__(self, **kwargs):
+        self.__dict__.update(kwargs)
+"""
+# Stand-in for a root's own token_compression/monkeypatch.py: its baseline branch, which imports the method relatively
+REF_MONKEYPATCH = """def replace_qwen25vl(args, model, method):
+    from . import fastv  # noqa: F401
+    print(f"using {method}")
+    return model
+"""
+
+
+def _caller_imports():
+    with open(IMPORTS) as f:
+        return json.load(f)
+
+
+def _write(path, text):
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(text)
+
+
+def _standin_root(base, root):
+    """<base>/<root>: a package root standing in for the reference's, with every baseline module its callers import
+    (each imported name a stub class), its own token_compression monkeypatch, and the OV model code for llava-ov-15."""
+    top = os.path.join(str(base), root)
+    for caller, rows in _caller_imports().items():
+        if dict(CALLERS)[caller] != root:
+            continue
+        for _, module, names in rows:
+            if module not in OURS:
+                path = os.path.join(top, *module.split(".")) + ".py"
+                _write(path, "".join(f"class {n}:\n    pass\n\n\n" for n in names if n != "*"))
+    if root == "qwen-evaluation":
+        _write(os.path.join(top, "token_compression", "monkeypatch.py"), REF_MONKEYPATCH)
+        _write(os.path.join(top, "token_compression", "fastv.py"), "")
+    if root == "llava-ov-15":
+        _write(os.path.join(top, "llavaonevision1_5", "__init__.py"), "")
+        _write(os.path.join(top, "llavaonevision1_5", "modeling_llavaonevision1_5.py"), OV_MODELING)
+        _write(os.path.join(top, "llavaonevision1_5", "configuration_llavaonevision1_5.py"), OV_CONFIG)
+    return top
+
+
+def _probe(caller, root, base):
+    """Run tests/_import_probe.py on a script holding the caller's recorded imports at their own line numbers."""
+    rows = _caller_imports()[caller]
+    lines = [""] * max(ln for ln, _, _ in rows)
+    for ln, module, names in rows:
+        lines[ln - 1] = f"from {module} import {', '.join(names)}"
+    script = os.path.join(str(base), "callers", caller)
+    _write(script, "\n".join(lines) + "\n")
+    ref_root = _standin_root(base, root)
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
     env.pop("PYTHONPATH", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_import_probe.py"), ROOT,
-                        os.path.join(REF, caller), os.path.join(REF, root)],
-                       capture_output=True, text=True, env=env, cwd="/tmp", timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_import_probe.py"), ROOT, script, ref_root],
+                       capture_output=True, text=True, env=env, cwd=str(base), timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("PROBE ")]
     assert lines, f"probe produced no result: rc={r.returncode}\n{r.stderr[-2000:]}"
-    return json.loads(lines[-1][6:])
+    return json.loads(lines[-1][6:]), ref_root
 
 
 @pytest.mark.parametrize("caller,root", CALLERS, ids=[c[0].split("/")[-1] for c in CALLERS])
-def test_reference_caller_imports_resolve(caller, root):
-    rows = _probe(caller, root)
+def test_reference_caller_imports_resolve(caller, root, tmp_path):
+    rows, ref_root = _probe(caller, root, tmp_path)
     assert rows, f"{caller}: no compression_method/token_compression imports found"
     for row in rows:
         where = f"{caller}:{row['line']}: {row['stmt']}"
@@ -66,16 +133,16 @@ def test_reference_caller_imports_resolve(caller, root):
                     assert mod.startswith(("visionselector_amd", "compression_method", "token_compression")), \
                         f"{where}: {name} comes from {mod}"
         else:
-            assert row["origin"] and row["origin"].startswith(REF), \
+            assert row["origin"] and row["origin"].startswith(ref_root), \
                 f"{where}: baseline module shadowed / not found ({row['origin']}, {row.get('find_error')})"
             if not row["ok"]:
                 assert not row["raised_in"].startswith(ROOT), f"{where} failed inside this repo: {row['error']}"
 
 
-def test_star_import_surface_of_ov_training_script():
+def test_star_import_surface_of_ov_training_script(tmp_path):
     """`from compression_method.selector_model import *` (llava-ov-15/src/train/train_sft_visionselector.py:14-15) must
     bring in every name that script then uses (:219-225)."""
-    rows = _probe("llava-ov-15/src/train/train_sft_visionselector.py", "llava-ov-15")
+    rows, _ = _probe("llava-ov-15/src/train/train_sft_visionselector.py", "llava-ov-15", tmp_path)
     names = {}
     for row in rows:
         names.update(row["names"])
@@ -84,9 +151,10 @@ def test_star_import_surface_of_ov_training_script():
         assert need in names, f"star import lost {need}"
 
 
-def test_ov_selector_classes_are_built_on_the_reference_bases():
+def test_ov_selector_classes_are_built_on_the_reference_bases(tmp_path):
     """The three names of llava-ov-15/compression_method/modeling_selector.py:68,188,339 resolve lazily, once, to
-    subclasses of the caller's own OV classes; the tower class constructs and carries the scorer's state-dict keys."""
+    subclasses of the caller's own OV classes (here the stand-in root's); the tower class constructs and carries the
+    scorer's state-dict keys."""
     code = r"""
 import sys
 sys.dont_write_bytecode = True
@@ -115,15 +183,16 @@ assert keys == ['importance_scorer.k_proj.bias', 'importance_scorer.k_proj.weigh
 assert tuple(t.importance_scorer.q_proj.weight.shape) == (32, 64)            # Linear(D, D // 2), modeling_selector.py:101
 assert t.budgets == 1.0
 print('OV-OK')
-""" % (DROPIN, ROOT, os.path.join(REF, "llava-ov-15"))
+""" % (DROPIN, ROOT, _standin_root(tmp_path, "llava-ov-15"))
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd="/tmp", timeout=600)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=600)
     assert "OV-OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
 
 
-def test_baseline_method_is_forwarded_to_the_reference_monkeypatch():
-    """`replace_qwen25vl(args, model, 'fastv')`: with the reference root behind dropin/, the reference's own branch
-    (qwen-evaluation/token_compression/monkeypatch.py:71-76) runs; without it, NotImplementedError as before."""
+def test_baseline_method_is_forwarded_to_the_reference_monkeypatch(tmp_path):
+    """`replace_qwen25vl(args, model, 'fastv')`: with a package root behind dropin/, that root's own branch
+    (the reference's qwen-evaluation/token_compression/monkeypatch.py:71-76) runs; without it, NotImplementedError as before."""
+    ref = _standin_root(tmp_path, "qwen-evaluation")
     code = r"""
 import sys, types, torch
 sys.dont_write_bytecode = True
@@ -136,8 +205,8 @@ ref = sys.modules['token_compression._reference_monkeypatch']
 assert ref.__file__.startswith(%r), ref.__file__
 assert sys.modules['token_compression.fastv'].__file__.startswith(%r)      # its relative imports resolved behind ours
 print('FWD-OK')
-""" % (DROPIN, ROOT, os.path.join(REF, "qwen-evaluation"), REF, REF)
+""" % (DROPIN, ROOT, ref, ref, ref)
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd="/tmp", timeout=600)
-    assert "using fastv" in r.stdout                     # the reference branch's own print (monkeypatch.py:72)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=600)
+    assert "using fastv" in r.stdout                     # the root's own branch ran (its print)
     assert "FWD-OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]

@@ -467,6 +467,32 @@ def test_bench_spawn_ranks_propagates_rank_exit_code(tmp_path, monkeypatch):
     assert bench.spawn_ranks(2, []) == 0
 
 
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """bench.dump_outputs: float32 / float64 files, at most 64 MB in all, an oversized array cut to the same seeded rows every
+    time (its `<name>_rows.npy` says which), the small ones written whole in their own shape."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    b, n, k, d = 16, 2304, 460, 3584                            # selected tokens: 105 MB as float32, over their share
+    scores = torch.randn(b, n, generator=g)
+    idx = torch.sort(torch.randperm(n, generator=g)[:k])[0].repeat(b, 1)
+    out = torch.randn(b, k, d, generator=g).bfloat16()
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), out, idx, scores)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["indices.npy", "scores.npy", "selected_tokens.npy", "selected_tokens_rows.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    assert np.array_equal(np.load(tmp_path / "a" / "scores.npy"), scores.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "indices.npy"), idx.numpy().astype(np.float64))
+    rows = np.load(tmp_path / "a" / "selected_tokens_rows.npy").astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and rows[-1] < b * k
+    assert np.array_equal(np.load(tmp_path / "a" / "selected_tokens.npy"), out.float().reshape(b * k, d).numpy()[rows])
+
+
 def test_every_kernel_of_the_lis_step_has_a_byte_model_in_bench():
     """bench.py builds `roofline` from the kernel the HIP-event clock names: every kernel name the LIS inference path can mark
     (VSEL_AFTER_LAUNCH in csrc/lis_kernels.h / lis_small.h) must be priced by bench.kernel_bytes, or `roofline.frac` could be empty again
