@@ -147,18 +147,6 @@ def test_tail_first_tiling_is_bit_identical_and_matches_oracle(ops):
     check(outs[1].float().cpu().numpy().astype(np.float64), refp, "[paged]")
 
 
-def test_attention_transpose_read_equals_plain_reads(ops):
-    """The ds_read_b64_tr_b16 V^T fragments and plain 16-bit column reads give bit-identical outputs."""
-    from visionselector_amd._native import debug_knob
-    q, k, v = make_qkv(600, 8, 2, 11)
-    cu = torch.tensor([0, 250, 600], dtype=torch.int32).cuda()
-    with debug_knob("attn_split", 0):                      # same single-stream schedule on both sides
-        a = ops.varlen_attn(q.cuda(), k.cuda(), v.cuda(), cu, 350)
-        with debug_knob("attn_use_tr", 0):
-            b = ops.varlen_attn(q.cuda(), k.cuda(), v.cuda(), cu, 350)
-    assert torch.equal(a, b)
-
-
 def test_attention_full_size_properties(ops):
     """Qwen2.5-VL-7B geometry at the uncompressed length (N + 64 = 2368): rows are convex combinations of V rows
     (|O| <= max|V|), first token attends only to itself, batch-of-sequences == separate calls."""

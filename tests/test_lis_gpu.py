@@ -347,9 +347,9 @@ def test_full_size_properties(ops, budget):
         assert all(abs(ref[j] - np.sort(ref)[::-1][k - 1]) <= 1e-5 for j in diff)
 
 
-def test_two_half_pipeline_equals_single_stream(ops):
-    """The opt-in aux-stream software pipeline (>= 32 segments, knob lis_pipeline / VSEL_PIPELINE=1) must give bit-identical
-    results to the single-stream, single-piece order."""
+def test_back_to_back_calls_are_bit_identical(ops):
+    """lis_select (35 images) and lis_select_varlen (36 ragged segments) called back to back on one stream, 20 times:
+    every result is bit-identical to the first (select and gather as two launches, knob lis_fused_select = 0)."""
     from visionselector_amd._native import debug_get, debug_knob
     c = oin.make_case(2048, 1024, 300, 5, batch=35)
     h, wq, bq, wk, bk = (dev(c[x], torch.bfloat16) for x in ("h", "wq", "bq", "wk", "bk"))
@@ -357,22 +357,13 @@ def test_two_half_pipeline_equals_single_stream(ops):
     ks = [max(1, n // 5) for n in lens]
     c2 = oin.make_case(2048, 1024, sum(lens), 6)
     h2 = dev(c2["h"], torch.bfloat16)
-    before = debug_get("lis_pipeline")
-    with debug_knob("lis_pipeline", 1):
-        a = ops.lis_select(h, wq, bq, wk, bk, 77)
-        a2 = ops.lis_select_varlen(h2, lens, ks, wq, bq, wk, bk)
-        with debug_knob("lis_pipeline", 0):
-            b = ops.lis_select(h, wq, bq, wk, bk, 77)
-            b2 = ops.lis_select_varlen(h2, lens, ks, wq, bq, wk, bk)
+    before = debug_get("lis_fused_select")
+    with debug_knob("lis_fused_select", 0):
+        outs = [ops.lis_select(h, wq, bq, wk, bk, 77) + ops.lis_select_varlen(h2, lens, ks, wq, bq, wk, bk) for _ in range(20)]
         torch.cuda.synchronize()
-        for x, y in zip(a + a2, b + b2):
-            assert torch.equal(x, y)
-        # back-to-back calls on the same stream reuse the aux stream / events correctly
-        outs = [ops.lis_select(h, wq, bq, wk, bk, 77) for _ in range(20)]
-        torch.cuda.synchronize()
-    assert debug_get("lis_pipeline") == before             # restored whatever happened inside
-    for o in outs:
-        for x, y in zip(o, a):
+    assert debug_get("lis_fused_select") == before         # restored whatever happened inside
+    for o in outs[1:]:
+        for x, y in zip(o, outs[0]):
             assert torch.equal(x, y)
 
 

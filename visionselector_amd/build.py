@@ -104,7 +104,7 @@ def _stale() -> bool:
 # issue and wait would read stale data, so these must compile without spilled VGPRs and without scratch.
 # (source file, mangled-name fragment).  The 8-wave dK/dV kernel (both instantiations) is on the list since round 4: its output
 # epilogue converts with v_cvt_pk_bf16_f32 instead of the software rounding whose constants pushed it to 256 + 25 registers.
-ASM_READ_KERNELS = (("attn.hip", "varlen_attn_fwd_kernelILb1E"), ("attn_bwd.hip", "attn_bwd_dkdv2_kernelILb0E"),
+ASM_READ_KERNELS = (("attn.hip", "varlen_attn_fwd_kernelI"), ("attn_bwd.hip", "attn_bwd_dkdv2_kernelILb0E"),
                     ("attn_bwd.hip", "attn_bwd_dkdv2_kernelILb1E"), ("attn_bwd.hip", "attn_bwd_dq_kernel"),
                     ("attn_fwd_gqa.hip", "attn_fwd_gqa_kernel"),
                     # the generated one-statement bodies clobber v32-255 / a0-255 / s40-99: everything the C++ around them keeps live must

@@ -72,7 +72,7 @@ __device__ unsigned long long g_fwd_tile_trace[8][8];
 // halve the work of a wave per round and 64-query workgroups use 252 CUs.
 // launch bounds: two waves per SIMD for the 4- / 8-wave workgroups; the single-wave GQA-packed decode workgroup owns 32 KiB of
 // LDS by itself, so waves-per-SIMD is LDS-bound there (5 workgroups per CU ~ 1 per SIMD) and asking for 2 only drew a warning
-template <bool USE_TR, int NW, int D, bool PACK = false, int KVS = 1, int KH = 1, bool TAIL = false>
+template <int NW, int D, bool PACK = false, int KVS = 1, int KH = 1, bool TAIL = false>
 __global__ __launch_bounds__(64 * NW, NW >= 4 ? 2 : 1) void varlen_attn_fwd_kernel(const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
                                                               const uint16_t* __restrict__ v,
                                                               const int32_t* __restrict__ cu, int hq, int hkv,
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 4 ? 2 : 1) void varlen_attn_fwd_kern
   constexpr int kLoadsPerWave = 16 / GW;           // 1-KiB wave-instructions per tile per tensor
   constexpr int NKB = 2 / KH;                      // 32-key blocks of a tile that one wave computes
   static_assert(KVS == 1 || (KVS == 2 && NW == 8 && !PACK), "two KV streams need 8 waves");
-  static_assert(KH == 1 || (KH == 2 && KVS == 2 && USE_TR && D == 128), "key halves: only in the two-stream form");
+  static_assert(KH == 1 || (KH == 2 && KVS == 2 && D == 128), "key halves: only in the two-stream form");
   constexpr int kHeadDim = D;
   constexpr int kSteps = D / 16;                   // k-steps of S^T = K Q^T
   constexpr int kDTiles = (D + 31) / 32;           // 32-wide d-tiles of O^T
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 4 ? 2 : 1) void varlen_attn_fwd_kern
       for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
-      if constexpr (USE_TR && kSteps == 8 && !PACK) {
+      if constexpr (kSteps == 8 && !PACK) {
         // per 32-key block: its 8 K fragments in ONE batch of ds_read_b128, then its 8 MFMAs (one LDS round trip per block instead
         // of one per MFMA; a second batch in flight would need 32 more registers and spills; batches of 4 with two in flight --
         // same registers, reads ahead of the MFMAs -- measured SLOWER, 880 vs 973 TFLOP/s at 16 x 4096)
@@ -375,7 +375,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 4 ? 2 : 1) void varlen_attn_fwd_kern
       VSEL_FWD_STAMP(2);
       // the first group of V fragments does not depend on P: put its transpose reads in flight now, under the softmax
       u32x2 vr0[8], vr1[8];
-      if constexpr (USE_TR && kDTiles == 4 && NW >= 8 && !PACK) {
+      if constexpr (kDTiles == 4 && NW >= 8 && !PACK) {
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
           vr0[2 * dt] = lds_read_tr16_b64_asm<(2 + CUR) * kBuf>(tr_addr_u[dt][0]);
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 4 ? 2 : 1) void varlen_attn_fwd_kern
       l_run += psum;
       VSEL_FWD_STAMP(3);
       // ---- O^T += V^T P^T -------------------------------------------------------------------------------------
-      if constexpr (USE_TR && kDTiles == 4 && !PACK) {
+      if constexpr (kDTiles == 4 && !PACK) {
         // four (32-key block, 16-key half) groups; a group = 8 transpose reads (4 d-tiles x lo / hi) feeding 4 MFMAs; the next
         // group's reads are in flight behind the current group's MFMAs
         auto issue = [&](auto g_c, u32x2 (&dst)[8]) {
@@ -492,20 +492,12 @@ __global__ __launch_bounds__(64 * NW, NW >= 4 ? 2 : 1) void varlen_attn_fwd_kern
           const int off = (32 * kb + 16 * mm) * kRowBytes;
 #pragma unroll
           for (int dt = 0; dt < kDTiles; ++dt) {
-            bf16x8_t vf;
-            if constexpr (USE_TR) {
-              // 16-lane group: lane p supplies the address of row (p >> 2), 4-column chunk (p & 3) of a [4 keys x 16 d]
-              // block and receives column p (4 keys) -- hardware transpose read
-              typedef __attribute__((address_space(3))) bf16x4_t* lds_p;
-              const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p)(vt + tr_addr[dt][0] + off));
-              const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p)(vt + tr_addr[dt][1] + off));
-              vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-            } else {
-              const int dcol = 32 * dt + j;
-#pragma unroll
-              for (int e = 0; e < 8; ++e)
-                vf[e] = *reinterpret_cast<const __bf16*>(vt + chunk_off(32 * kb + 16 * mm + 8 * hh + e, dcol >> 3) + (dcol & 7) * 2);
-            }
+            // 16-lane group: lane p supplies the address of row (p >> 2), 4-column chunk (p & 3) of a [4 keys x 16 d]
+            // block and receives column p (4 keys) -- hardware transpose read
+            typedef __attribute__((address_space(3))) bf16x4_t* lds_p;
+            const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p)(vt + tr_addr[dt][0] + off));
+            const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_p)(vt + tr_addr[dt][1] + off));
+            const bf16x8_t vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
             o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[kb][mm], o[dt], 0, 0, 0);
           }
         }
@@ -667,7 +659,7 @@ extern "C" int vsel_debug_read_attn_trace(unsigned long long* out, int clear) {
 static int attn_launch(hipStream_t st, const void* q, const void* k, const void* v, const int32_t* cu_q, int64_t n_seq,
                        int64_t max_seqlen_q, int64_t hq, int64_t hkv, int64_t d, float scale, int causal, void* out,
                        const PagedKV& pg, float* lse = nullptr, int64_t total = 0) {
-  const bool g_attn_use_tr = knob(VSEL_KNOB_ATTN_USE_TR) != 0, g_attn_split_q64 = knob(VSEL_KNOB_ATTN_SPLIT_Q64) != 0;
+  const bool g_attn_split_q64 = knob(VSEL_KNOB_ATTN_SPLIT_Q64) != 0;
   const int g_attn_nw = knob(VSEL_KNOB_ATTN_WAVES), g_attn_pack = knob(VSEL_KNOB_ATTN_PACK), g_attn_split = knob(VSEL_KNOB_ATTN_SPLIT);
   // 8-wave workgroups (256 queries) when there is enough work to fill the chip with them, else 4-wave (128 queries)
   const int64_t items8 = cdiv(max_seqlen_q, 256) * hq * n_seq;
@@ -685,7 +677,7 @@ static int attn_launch(hipStream_t st, const void* q, const void* k, const void*
   const int64_t items4 = cdiv(max_seqlen_q, 128) * hq * n_seq;
   // (not for the LSE-saving training forward: the split changes the summation order, and training keeps "a sequence's
   // results do not depend on what it is packed with" bit for bit)
-  const bool split2 = g_attn_split != 0 && d == 128 && !pack && !big && g_attn_nw == 0 && g_attn_use_tr && items4 <= 256 &&
+  const bool split2 = g_attn_split != 0 && d == 128 && !pack && !big && g_attn_nw == 0 && items4 <= 256 &&
                       (g_attn_split == 1 || (lse == nullptr && (pg.seqlens_k != nullptr || max_seqlen_q >= 256)));
   // ... and 64-query workgroups whose wave pairs split every tile's keys (KH = 2) while those still fit one per CU
   const bool split2_q64 = split2 && g_attn_split_q64 && cdiv(max_seqlen_q, 64) * hq * n_seq <= 256;
@@ -707,7 +699,7 @@ static int attn_launch(hipStream_t st, const void* q, const void* k, const void*
   // One sequence (68 items) stays with the two-stream per-head form (13.5 vs 19 us); from 2048 tokens attn_fwd64 (256-query items).
   const int g_gqa = knob(VSEL_KNOB_ATTN_GQA);
   const int64_t rep_ = hq / hkv;
-  if (d == 128 && g_attn_use_tr && !pg.block_table && !pg.seqlens_k && !pg.cu_k && g_attn_nw == 0 && rep_ >= 2 && rep_ <= 8 &&
+  if (d == 128 && !pg.block_table && !pg.seqlens_k && !pg.cu_k && g_attn_nw == 0 && rep_ >= 2 && rep_ <= 8 &&
       max_seqlen_q <= 16384 && g_rows64 != 1) {
     // items of the 8-wave form that hold work (ragged batches: from the token count when the entry point knows it -- the item LIST is
     // sized by the longest sequence, but a shorter sequence's items at the levels it does not reach are skipped in runs)
@@ -737,7 +729,7 @@ static int attn_launch(hipStream_t st, const void* q, const void* k, const void*
                                                                                    out, pg, lse, deal);
     }
   }
-  if (d == 128 && g_attn_use_tr && !pack && !pg.block_table && g_attn_nw == 0 &&
+  if (d == 128 && !pack && !pg.block_table && g_attn_nw == 0 &&
       (g_rows64 == 1 || (g_rows64 < 0 && max_seqlen_q >= 2048 && !split2)))
     return attn::attn_fwd64_launch(st, q, k, v, cu_q, n_seq, max_seqlen_q, hq, hkv, scale, causal, out, pg, lse);
   const int block_q = big ? 256 : (split2_q64 ? 64 : 128);
@@ -772,38 +764,36 @@ static int attn_launch(hipStream_t st, const void* q, const void* k, const void*
   // run time; the 8-wave instantiation measured -3 % at 16 x 4096 (where both tilings are the same tiles) and +2 % at 16 x 2368, so
   // it keeps the start-aligned tiling unless forced (same-box A/B, tools/ab_attn.sh)
   const int g_tail = knob(VSEL_KNOB_ATTN_TAIL_FIRST);
-  const bool tail_first = causal && !pack && !split2 && d == 128 && g_attn_use_tr && (g_tail == 1 || (g_tail < 0 && !big && n_items > 2 * slots));
-#define VSEL_ATTN_LAUNCH(TR, NWV, DV)                                                                                          \
-  VSEL_LAUNCH((varlen_attn_fwd_kernel<TR, NWV, DV>), grid, dim3(64 * NWV), 0, st, (const uint16_t*)q, (const uint16_t*)k, \
+  const bool tail_first = causal && !pack && !split2 && d == 128 && (g_tail == 1 || (g_tail < 0 && !big && n_items > 2 * slots));
+#define VSEL_ATTN_LAUNCH(NWV, DV)                                                                                              \
+  VSEL_LAUNCH((varlen_attn_fwd_kernel<NWV, DV>), grid, dim3(64 * NWV), 0, st, (const uint16_t*)q, (const uint16_t*)k, \
                      (const uint16_t*)v, cu_q, (int)hq, (int)hkv, sl2, causal, (uint16_t*)out, q_tiles, (int)n_seq, slot, pg, lse)
   if (split2_q64) {
-    VSEL_LAUNCH((varlen_attn_fwd_kernel<true, 8, 128, false, 2, 2>), grid, dim3(512), 0, st, (const uint16_t*)q,
+    VSEL_LAUNCH((varlen_attn_fwd_kernel<8, 128, false, 2, 2>), grid, dim3(512), 0, st, (const uint16_t*)q,
                        (const uint16_t*)k, (const uint16_t*)v, cu_q, (int)hq, (int)hkv, sl2, causal, (uint16_t*)out, q_tiles,
                        (int)n_seq, slot, pg, lse);
   } else if (split2) {
-    VSEL_LAUNCH((varlen_attn_fwd_kernel<true, 8, 128, false, 2>), grid, dim3(512), 0, st, (const uint16_t*)q,
+    VSEL_LAUNCH((varlen_attn_fwd_kernel<8, 128, false, 2>), grid, dim3(512), 0, st, (const uint16_t*)q,
                        (const uint16_t*)k, (const uint16_t*)v, cu_q, (int)hq, (int)hkv, sl2, causal, (uint16_t*)out, q_tiles,
                        (int)n_seq, slot, pg, lse);
   } else if (pack) {
-    VSEL_LAUNCH((varlen_attn_fwd_kernel<true, 1, 128, true>), grid, dim3(64), 0, st, (const uint16_t*)q, (const uint16_t*)k,
+    VSEL_LAUNCH((varlen_attn_fwd_kernel<1, 128, true>), grid, dim3(64), 0, st, (const uint16_t*)q, (const uint16_t*)k,
                        (const uint16_t*)v, cu_q, (int)hq, (int)hkv, sl2, causal, (uint16_t*)out, q_tiles, (int)n_seq, slot, pg, lse);
   } else if (d == 128) {
-    if (g_attn_use_tr && tail_first) {
+    if (tail_first) {
 #define VSEL_ATTN_LAUNCH_TAIL(NWV)                                                                                                  \
-  VSEL_LAUNCH((varlen_attn_fwd_kernel<true, NWV, 128, false, 1, 1, true>), grid, dim3(64 * NWV), 0, st, (const uint16_t*)q, \
+  VSEL_LAUNCH((varlen_attn_fwd_kernel<NWV, 128, false, 1, 1, true>), grid, dim3(64 * NWV), 0, st, (const uint16_t*)q, \
                      (const uint16_t*)k, (const uint16_t*)v, cu_q, (int)hq, (int)hkv, sl2, causal, (uint16_t*)out, q_tiles,        \
                      (int)n_seq, slot, pg, lse)
       if (big) VSEL_ATTN_LAUNCH_TAIL(8); else VSEL_ATTN_LAUNCH_TAIL(4);
 #undef VSEL_ATTN_LAUNCH_TAIL
-    } else if (g_attn_use_tr) {
-      if (big) VSEL_ATTN_LAUNCH(true, 8, 128); else VSEL_ATTN_LAUNCH(true, 4, 128);
     } else {
-      if (big) VSEL_ATTN_LAUNCH(false, 8, 128); else VSEL_ATTN_LAUNCH(false, 4, 128);
+      if (big) VSEL_ATTN_LAUNCH(8, 128); else VSEL_ATTN_LAUNCH(4, 128);
     }
   } else if (d == 80) {          // Qwen2.5-VL vision tower
-    if (big) VSEL_ATTN_LAUNCH(true, 8, 80); else VSEL_ATTN_LAUNCH(true, 4, 80);
+    if (big) VSEL_ATTN_LAUNCH(8, 80); else VSEL_ATTN_LAUNCH(4, 80);
   } else {                       // d == 64: Rice ViT (LLaVA-OV-1.5)
-    if (big) VSEL_ATTN_LAUNCH(true, 8, 64); else VSEL_ATTN_LAUNCH(true, 4, 64);
+    if (big) VSEL_ATTN_LAUNCH(8, 64); else VSEL_ATTN_LAUNCH(4, 64);
   }
 #undef VSEL_ATTN_LAUNCH
   queue_slot_launched(kSlotFwd, taken, st);

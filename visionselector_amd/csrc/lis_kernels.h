@@ -857,16 +857,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const T* __restrict__ 
 // Cache policy of the three kernels that touch the token tensor: non-temporal once the tensor clearly exceeds the Infinity
 // Cache (256 MB) + L2 (32 MB).  Measured crossover between 264 MB (default policy 4 % faster) and 528 MB (nt 12 % faster).
 constexpr int64_t kStreamBytes = 384ll << 20;
-// The policy is a property of the WHOLE API call: when a call is cut into halves (lis.hip) the halves inherit the call's row count.
-inline thread_local int64_t tl_policy_rows = -1;
-struct PolicyScope {
-  explicit PolicyScope(int64_t rows) { tl_policy_rows = rows; }
-  ~PolicyScope() { tl_policy_rows = -1; }
-};
-inline bool stream_policy(int64_t total_rows, int64_t d, size_t elem) {
-  const int64_t rows = tl_policy_rows >= 0 ? tl_policy_rows : total_rows;
-  return rows * d * (int64_t)elem >= kStreamBytes;
-}
+inline bool stream_policy(int64_t total_rows, int64_t d, size_t elem) { return total_rows * d * (int64_t)elem >= kStreamBytes; }
 
 struct LisPlan {
   int64_t S, maxn, d, hd;
@@ -882,8 +873,8 @@ inline LisPlan make_plan(int64_t S, int64_t maxn, int64_t d, int64_t hd) {
   LisPlan p{};
   p.S = S; p.maxn = maxn; p.d = d; p.hd = hd;
   // Batch-invariant plan: the summation tree of one segment never depends on how many segments share the call
-  // (fixed 128-row chunks in sweep 1, fixed split-K slices in the projections), so batching, the two-half pipeline
-  // and the ragged form all reproduce a single-image call bit for bit.
+  // (fixed 128-row chunks in sweep 1, fixed split-K slices in the projections), so batching and the ragged form
+  // reproduce a single-image call bit for bit.
   p.row_splits = (int)std::max<int64_t>(1, cdiv(maxn, kRowsPerChunk));
   p.mfma_bf16 = (d % 16 == 0) && (hd % 16 == 0);
   p.kslice1 = (int)std::min<int64_t>(kSliceNT, cdiv(d, 16) * 16);
@@ -1100,13 +1091,6 @@ inline int run_scores(hipStream_t st, const T* h, const vsel_segments* seg, cons
   rc = run_proj<TW>(st, seg, sc, ws, p);
   if (rc) return rc;
   return run_score<T>(st, h, seg, sc, ws, p, scores);
-}
-
-template <typename T>
-inline int run_scores_w(hipStream_t st, const T* h, const vsel_segments* seg, const vsel_scorer* sc, char* ws,
-                        const LisPlan& p, float* scores) {
-  if (sc->wdtype == VSEL_BF16) return run_scores<T, bf16_t>(st, h, seg, sc, ws, p, scores);
-  return run_scores<T, float>(st, h, seg, sc, ws, p, scores);
 }
 
 inline int launch_select(hipStream_t st, const float* scores, const vsel_segments* seg, int64_t* idx, float* mask) {
