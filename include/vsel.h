@@ -341,6 +341,44 @@ int vsel_varlen_attn_fwd_strided(void* stream, const void* q, const void* k, con
                                  int64_t k_row_stride, int64_t k_head_stride, int64_t v_row_stride, int64_t v_head_stride,
                                  float scale, int causal, void* out);
 
+/* -------- decode against a KV cache: in-place append, then attention (flash_attn_with_kvcache) --------------------
+ * flash-attn 2.7.4's flash_attn_with_kvcache (the decode entry point of code written against flash-attn; no reference call site:
+ * the reference decodes through an HF DynamicCache).  Two launches: kvcache_append_kernel, then the var-len forward above.
+ *   q            [batch, seqlen_q, hq, d] bf16, element (b, i, h) at b * q_batch_stride + i * q_row_stride + h * q_head_stride;
+ *                never modified.  May be NULL when out is NULL (append only).
+ *   k_cache / v_cache  bf16, contiguous, one of two layouts:
+ *                contiguous  [cache_rows = B_cache, cache_len = L_cache, hkv, d], block_table NULL: batch row b lives in cache row
+ *                            cache_batch_idx[b] (NULL: b) and sees cache positions [cache_leftpad[b] (NULL: 0), end + seqlen_new);
+ *                paged       [cache_rows = n_blocks, cache_len = page_size, hkv, d], block_table DEVICE int32 [batch, max_pages]:
+ *                            position p of row b is page block_table[b][p / page_size], offset p % page_size.  The row's
+ *                            capacity is its leading run of entries in [0, n_blocks) (tables may be padded with -1).
+ *                            cache_batch_idx / cache_leftpad must be NULL (VSEL_ERR_UNSUPPORTED, as flash-attn refuses them).
+ *   k / v        [batch, seqlen_new, hkv, d] bf16 (strided like q) or NULL with seqlen_new == 0: row j of batch row b is written
+ *                IN PLACE at cache position end + j, end = cache_seqlens[b] (DEVICE int32 [batch]; NULL: the host value
+ *                cache_seqlen for every row).  No other cache element changes.
+ *   rotary_cos / rotary_sin  NULL, or [seqlen_ro, rotary_dim / 2] (rotary_dtype: bf16 or fp32), rotary_dim even and <= d: new
+ *                key j is rotated at table row end + j before it is written; the attention reads a rotated COPY of q (rows
+ *                end + i when causal, end otherwise).  rotary_interleaved: pairs (2i, 2i + 1), else (i, i + rotary_dim / 2);
+ *                features past rotary_dim pass through; fp32 arithmetic, one bf16 rounding.
+ *   out          [batch, seqlen_q, hq, d] bf16 = softmax(scale q k^T) v over the visible keys, causal masking bottom-right
+ *                aligned (query i sees key index < i + 1 + K - seqlen_q, K = visible keys); NULL: append only.
+ *   lse          NULL, or fp32 [batch * seqlen_q, hq] (natural log of the scaled scores' sum).  A row that sees no key outputs
+ *                zeros and lse -inf.  d in {64, 80, 128}; strides multiples of 8 elements, tensors 16-byte aligned.
+ * Device values are never read on the host: a row whose end + seqlen_new exceeds its capacity (or whose cache_batch_idx is out of
+ * [0, B_cache)) is written only inside its capacity and attends to at most that many keys -- a caller error with an unspecified
+ * result for that row, never an access outside k_cache / v_cache / the tables.  Workspace (256-byte aligned):
+ * vsel_kvcache_attn_workspace_bytes(batch, seqlen_q, hq, d) -- per-row metadata and the q copy.                              */
+size_t vsel_kvcache_attn_workspace_bytes(int64_t batch, int64_t seqlen_q, int64_t hq, int64_t d);
+int vsel_kvcache_attn_fwd(void* stream, const void* q, int64_t q_batch_stride, int64_t q_row_stride, int64_t q_head_stride,
+                          void* k_cache, void* v_cache, int64_t cache_rows, int64_t cache_len, const int32_t* block_table,
+                          int64_t max_pages, const void* k, const void* v, int64_t seqlen_new, int64_t k_batch_stride,
+                          int64_t k_row_stride, int64_t k_head_stride, int64_t v_batch_stride, int64_t v_row_stride,
+                          int64_t v_head_stride, const int32_t* cache_seqlens, int64_t cache_seqlen, const int32_t* cache_batch_idx,
+                          const int32_t* cache_leftpad, const void* rotary_cos, const void* rotary_sin, vsel_dtype rotary_dtype,
+                          int64_t seqlen_ro, int64_t rotary_dim, int rotary_interleaved, int64_t batch, int64_t seqlen_q,
+                          int64_t hq, int64_t hkv, int64_t d, float scale, int causal, void* out, float* lse, void* workspace,
+                          size_t workspace_bytes);
+
 /* -------- the same forward with a caller workspace: key-range parts for ONE long sequence ------------------------
  * vsel_varlen_attn_fwd (and _lse when lse != NULL) on batches the launch cannot balance as they are -- one uncompressed prompt, or a
  * few of equal length: 256-query items cut over key ranges, fp32 partial outputs + (m, l) in `ws`, merged in part order by a second

@@ -1,0 +1,183 @@
+"""Decode on a KV cache: flash_attn_with_kvcache at kernel level, packed_generate at model level.  One JSON line per measurement.
+
+    python tools/bench_generate.py [--kernel] [--model] [--batches 1,8,32] [--new-tokens 64]
+
+Kernel level (7B heads: 28 q / 4 kv, d 128, s_q = s_new = 1): B in {1, 8, 32, 64, 256} x cache length in {524, 2368}, three
+layouts -- paged (page 64, scattered pages), contiguous, contiguous with left padding (cache_leftpad + cache_batch_idx) --
+against ops.paged_attn over the same number of keys on the same kind of pages (the attention launch alone).  The append launch
+is timed on its own (append-only call) and, from the library's per-kernel profile (device time, host gaps excluded), priced by
+the bytes it moves: the new K / V rows read and written, 2 x 2 x B x Hkv x d x 2 bytes, plus 16 bytes of metadata per row.
+Model level: a Qwen2.5-VL-7B-geometry selector model with random bf16 weights (built as tools/bench_e2e.py builds it), B prompts
+of 2304 visual tokens + 64 text tokens, budget 0.2, N new tokens: packed_generate tokens/s against B sequential batch-1
+model.generate() calls (greedy, min_new_tokens = max_new_tokens so that both produce the same count).
+Every line carries the box (host, device) and the commit (VSEL_COMMIT, since the tree may travel without its .git)."""
+import argparse
+import json
+import os
+import socket
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from visionselector_amd import _native as N  # noqa: E402
+from visionselector_amd import ops  # noqa: E402
+from visionselector_amd.flash_attn_compat import flash_attn_with_kvcache  # noqa: E402
+
+HQ, HKV, D, PAGE = 28, 4, 128, 64
+
+
+def _stamp(rec):
+    rec.update(box=f"{socket.gethostname()} / {torch.cuda.get_device_name(0)}", commit=os.environ.get("VSEL_COMMIT", "unknown"))
+    print(json.dumps(rec), flush=True)
+
+
+def _time_us(fn, iters=50, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3
+
+
+def kernel_level():
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rnd = lambda *s: torch.randn(*s, device="cuda", generator=g).bfloat16()  # noqa: E731
+    for b in (1, 8, 32, 64, 256):
+        for lk in (524, 2368):
+            q, k, v = rnd(b, 1, HQ, D), rnd(b, 1, HKV, D), rnd(b, 1, HKV, D)
+            end = torch.full((b,), lk - 1, dtype=torch.int32, device="cuda")          # lk visible keys after the append
+            # paged: scattered pages, -1-padded tables
+            per = -(-lk // PAGE)
+            n_pages = b * per
+            kp, vp = rnd(n_pages, PAGE, HKV, D), rnd(n_pages, PAGE, HKV, D)
+            bt = torch.full((b, per + 1), -1, dtype=torch.int32, device="cuda")
+            bt[:, :per] = torch.randperm(n_pages, device="cuda", generator=g).to(torch.int32).view(b, per)
+            # contiguous: [B, L_cache, Hkv, d]; left-padded: 64 leading pad positions, rows permuted through cache_batch_idx
+            kc, vc = rnd(b, lk, HKV, D), rnd(b, lk, HKV, D)
+            pad = 64
+            kl, vl = rnd(b + 1, lk + pad, HKV, D), rnd(b + 1, lk + pad, HKV, D)
+            bidx = torch.randperm(b + 1, device="cuda", generator=g)[:b].to(torch.int32)
+            lp = torch.full((b,), pad, dtype=torch.int32, device="cuda")
+            cu_q = torch.arange(0, b + 1, dtype=torch.int32, device="cuda")
+            klens = torch.full((b,), lk, dtype=torch.int32, device="cuda")
+            base = _time_us(lambda: ops.paged_attn(q.view(b, HQ, D), kp, vp, cu_q, klens, bt, 1))
+            rec = {"bench": "kvcache_decode", "batch": b, "cache_len": lk, "heads": f"{HQ}/{HKV}", "d": D,
+                   "paged_attn_us": round(base, 2)}
+            for tag, fn in (("paged64", lambda: flash_attn_with_kvcache(q, kp, vp, k, v, cache_seqlens=end, block_table=bt, causal=True)),
+                            ("contiguous", lambda: flash_attn_with_kvcache(q, kc, vc, k, v, cache_seqlens=end, causal=True)),
+                            ("contiguous_leftpad", lambda: flash_attn_with_kvcache(q, kl, vl, k, v, cache_seqlens=end + pad, cache_leftpad=lp,
+                                                                                   cache_batch_idx=bidx, causal=True))):
+                rec[f"{tag}_us"] = round(_time_us(fn), 2)
+                rec[f"{tag}_vs_paged_attn"] = round(rec[f"{tag}_us"] / base, 3)
+            app = _time_us(lambda: ops.kvcache_attn(None, kp, vp, k=k, v=v, cache_seqlens=end, block_table=bt))
+            rec["append_only_call_us"] = round(app, 2)
+            # device time per launch (libvsel's event brackets around each kernel, host gaps excluded): the wall times above are
+            # host-bound at small B (one Python call per launch)
+            for tag, fn in (("paged_attn", lambda: ops.paged_attn(q.view(b, HQ, D), kp, vp, cu_q, klens, bt, 1)),
+                            ("paged64", lambda: flash_attn_with_kvcache(q, kp, vp, k, v, cache_seqlens=end, block_table=bt, causal=True)),
+                            ("contiguous_leftpad", lambda: flash_attn_with_kvcache(q, kl, vl, k, v, cache_seqlens=end + pad, cache_leftpad=lp,
+                                                                                   cache_batch_idx=bidx, causal=True))):
+                fn()
+                torch.cuda.synchronize()
+                N.profile_start()
+                for _ in range(20):
+                    fn()
+                prof = N.profile_stop()
+                ms, calls = prof["varlen_attn_fwd_kernel"]
+                rec[f"{tag}_attn_kernel_us"] = round(ms / calls * 1e3, 2)
+                if "kvcache_append_kernel" in prof:
+                    ms, calls = prof["kvcache_append_kernel"]
+                    rec[f"{tag}_append_kernel_us"] = round(ms / calls * 1e3, 2)
+            moved = 2 * 2 * b * HKV * D * 2 + 4 * 4 * b
+            ak = rec["paged64_append_kernel_us"]
+            rec.update(append_bytes=moved, append_GBps=round(moved / ak / 1e3, 2),
+                       append_share_of_paged64_device=round(ak / (ak + rec["paged64_attn_kernel_us"]), 3),
+                       leftpad_attn_vs_paged_attn_device=round(rec["contiguous_leftpad_attn_kernel_us"] / rec["paged_attn_attn_kernel_us"], 3))
+            _stamp(rec)
+
+
+def model_level(batches, new_tokens):
+    from transformers import Qwen2_5_VLConfig
+    from visionselector_amd.attention import ATTN_NAME, ATTN_NAME_PACKED, replace_qwen2_vl_attention_class
+    from visionselector_amd.generate import packed_generate
+    from visionselector_amd.hf_qwen25vl import Qwen2_5_VLForConditionalGeneration_Selector
+    IMG, VID, VSTART, VEND = 151655, 151656, 151652, 151653
+    replace_qwen2_vl_attention_class()
+    cfg = Qwen2_5_VLConfig(
+        text_config=dict(hidden_size=3584, intermediate_size=18944, num_hidden_layers=28, num_attention_heads=28,
+                         num_key_value_heads=4, vocab_size=152064, max_position_embeddings=32768,
+                         rope_parameters=dict(rope_type="default", mrope_section=[16, 24, 24], rope_theta=1000000.0)),
+        vision_config=dict(depth=32, hidden_size=1280, num_heads=16, intermediate_size=3420, out_hidden_size=3584, patch_size=14,
+                           spatial_merge_size=2, temporal_patch_size=2, window_size=112, fullatt_block_indexes=[7, 15, 23, 31],
+                           in_channels=3),
+        image_token_id=IMG, video_token_id=VID, vision_start_token_id=VSTART, vision_end_token_id=VEND)
+    torch.manual_seed(0)
+    torch.set_default_dtype(torch.bfloat16)
+    with torch.device("cuda"):
+        model = Qwen2_5_VLForConditionalGeneration_Selector(cfg).eval()
+    torch.set_default_dtype(torch.float32)
+    model.model.language_model.config._attn_implementation = ATTN_NAME
+    model.model.visual.config._attn_implementation = ATTN_NAME_PACKED
+    with torch.no_grad():
+        for p in model.visual.importance_scorer.parameters():
+            p.copy_(0.02 * torch.randn_like(p))
+    model.visual.budgets = 0.2
+    grid, n_vis, n_text = (1, 96, 96), 96 * 96 // 4, 64
+    g = torch.Generator().manual_seed(1)
+    prompts, pix = [], []
+    for _ in range(max(batches)):
+        pre = torch.randint(1000, 5000, (n_text // 2,), generator=g)
+        post = torch.randint(1000, 5000, (n_text - n_text // 2 - 2,), generator=g)
+        prompts.append(torch.cat((pre, torch.tensor([VSTART]), torch.full((n_vis,), IMG), torch.tensor([VEND]), post)))
+        pix.append(torch.randn(96 * 96, 3 * 2 * 14 * 14, generator=g).bfloat16())
+    grid_t = torch.tensor([list(grid)]).cuda()
+
+    def packed(b, n=new_tokens):
+        out = packed_generate(model, prompts[:b], torch.cat(pix[:b]).cuda(), grid_t.repeat(b, 1), [1] * b, max_new_tokens=n)
+        assert all(len(t) == n for t in out["tokens"])
+
+    def sequential(b):
+        for i in range(b):
+            ids = prompts[i][None].cuda()
+            model.model.rope_deltas = None
+            with torch.no_grad():
+                model.generate(input_ids=ids, attention_mask=torch.ones_like(ids), pixel_values=pix[i].cuda(), image_grid_thw=grid_t,
+                               mm_token_type_ids=(ids == IMG).int(), max_new_tokens=new_tokens, min_new_tokens=new_tokens, do_sample=False)
+
+    sequential(1)                                                   # warm-up (kernels, allocator, library heuristics)
+    for b in batches:
+        packed(b, 2)            # warm-up at this batch's shapes (the tower's first call at a new image count costs seconds)
+        res = {"bench": "packed_generate", "batch": b, "visual_tokens": n_vis, "text_tokens": n_text, "budget": 0.2,
+               "new_tokens": new_tokens, "model": "Qwen2.5-VL-7B geometry, random-init bf16"}
+        for tag, fn in (("packed_generate", packed), ("sequential_generate", sequential)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(b)
+            torch.cuda.synchronize()
+            s = time.perf_counter() - t0
+            res[f"{tag}_s"] = round(s, 3)
+            res[f"{tag}_tok_per_s"] = round(b * new_tokens / s, 1)
+        res["speedup"] = round(res["sequential_generate_s"] / res["packed_generate_s"], 2)
+        _stamp(res)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kernel", action="store_true")
+    ap.add_argument("--model", action="store_true")
+    ap.add_argument("--batches", default="1,8,32")
+    ap.add_argument("--new-tokens", type=int, default=64)
+    a = ap.parse_args()
+    if not a.kernel and not a.model:
+        a.kernel = a.model = True
+    if a.kernel:
+        kernel_level()
+    if a.model:
+        model_level([int(x) for x in a.batches.split(",")], a.new_tokens)

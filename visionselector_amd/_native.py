@@ -73,6 +73,10 @@ SIGNATURES = {
     "vsel_varlen_attn_fwd_strided": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64,
                                                _I64, _F, C.c_int, _P]),
     "vsel_paged_attn_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _F, C.c_int, _P]),
+    "vsel_kvcache_attn_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "vsel_kvcache_attn_fwd": (C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64,
+                                        _I64, _P, _I64, _P, _P, _P, _P, C.c_int, _I64, _I64, C.c_int, _I64, _I64, _I64, _I64, _I64, _F,
+                                        C.c_int, _P, _P, _P, _SZ]),
 }
 
 # include/vsel_debug.h (diagnostic knobs; not part of the drop-in boundary)

@@ -801,6 +801,12 @@ static int attn_launch(hipStream_t st, const void* q, const void* k, const void*
   return VSEL_OK;
 }
 
+int attn::attn_launch_cache(hipStream_t st, const void* q, const void* k, const void* v, const int32_t* cu_q, int64_t n_seq,
+                            int64_t max_seqlen_q, int64_t hq, int64_t hkv, int64_t d, float scale, int causal, void* out, const PagedKV& pg,
+                            float* lse) {
+  return attn_launch(st, q, k, v, cu_q, n_seq, max_seqlen_q, hq, hkv, d, scale, causal, out, pg, lse);
+}
+
 static int attn_checks(const void* q, const void* k, const void* v, const int32_t* cu, const void* out, int64_t n_seq,
                        int64_t max_seqlen, int64_t hq, int64_t hkv, int64_t d) {
   if (!q || !k || !v || !cu || !out) return fail(VSEL_ERR_INVALID, "NULL pointer");

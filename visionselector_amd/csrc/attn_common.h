@@ -88,6 +88,11 @@ struct PagedKV {
   int64_t q_row_stride, q_head_stride, kv_row_stride, kv_head_stride, v_row_stride, v_head_stride;   // v_*: 0 = same as k
 };
 
+// attn.hip's form selection and launch, for the attention half of vsel_kvcache_attn_fwd (kvcache.hip): queries packed per cu_q,
+// keys per pg (seqlens_k always set; page table or contiguous rows at cu_k)
+int attn_launch_cache(hipStream_t st, const void* q, const void* k, const void* v, const int32_t* cu_q, int64_t n_seq, int64_t max_seqlen_q,
+                      int64_t hq, int64_t hkv, int64_t d, float scale, int causal, void* out, const PagedKV& pg, float* lse);
+
 // 64-rows-per-wave forward for head_dim 128 (attn_fwd64.hip): contiguous keys only (no page table); same items as the 8-wave form
 int attn_fwd64_launch(hipStream_t st, const void* q, const void* k, const void* v, const int32_t* cu_q, int64_t n_seq,
                       int64_t max_seqlen_q, int64_t hq, int64_t hkv, float scale, int causal, void* out, const PagedKV& pg, float* lse);

@@ -5,6 +5,7 @@ The reference imports, from flash_attn==2.7.4.post1 (requirements.txt:5):
                                                                qwen-vl-finetune/qwenvl/train/trainer.py:7 (…flash_attn_interface)
     flash_attn.bert_padding.{index_first_axis, pad_input, unpad_input}     qwen-evaluation/token_compression/selector_model.py:26
     flash_attn.layers.rotary.apply_rotary_emb                               qwen-vl-finetune/compression_method/selector_model.py:31
+and, for code that decodes against a KV cache, flash_attn.flash_attn_with_kvcache (no reference call site).
 flash_attn has no ROCm build in this image; `visionselector_amd/dropin/flash_attn/` exposes the functions below under the
 same module paths so the reference's vendored modeling files import and run unchanged.  Signatures follow the published
 flash-attn 2.7 Python API; unsupported options (dropout, sliding window, softcap, alibi, attention probabilities) raise.
@@ -68,6 +69,56 @@ def flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wi
     out = flash_attn_varlen_func(q.reshape(b * sq, h, d), k.reshape(b * sk, k.shape[2], d), v.reshape(b * sk, v.shape[2], d),
                                  cu_q, cu_k, sq, sk, softmax_scale=softmax_scale, causal=causal)
     return out.view(b, sq, h, d)
+
+
+_KVCACHE_HEAD_DIMS = (64, 80, 128)
+
+
+def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,
+                            cache_batch_idx=None, cache_leftpad=None, block_table=None, softmax_scale=None, causal=False,
+                            window_size=(-1, -1), softcap=0.0, rotary_interleaved=True, alibi_slopes=None, num_splits=0,
+                            return_softmax_lse=False):
+    """flash-attn's decode entry point (vsel_kvcache_attn_fwd: one append launch, then the var-len attention kernel).
+
+    q [B, s_q, H, d]; k_cache / v_cache [B_cache, L_cache, Hk, d], or [n_blocks, page_size, Hk, d] with block_table int32
+    [B, max_pages] (entries past the used pages may be -1); k / v [B, s_new, Hk, d] are written into the cache IN PLACE at
+    positions cache_seqlens[b] + j (cache row cache_batch_idx[b] of a contiguous cache), rotated first when rotary_cos /
+    rotary_sin [seqlen_ro, rotary_dim / 2] are given (then the attention uses a rotated copy of q: rows cache_seqlens + i when
+    causal, cache_seqlens otherwise; q itself is never modified).  Batch row b attends to cache positions
+    [cache_leftpad[b], cache_seqlens[b] + s_new); causal masking is bottom-right aligned.  -> out [B, s_q, H, d]
+    (and softmax_lse fp32 [B, H, s_q] with return_softmax_lse).  A row with no visible key outputs zeros (lse -inf).
+
+    Readings of the flash-attn 2.7.4 docstring taken here: cache_seqlens=None means the whole cache is in use; the rotary table
+    row of new key j is cache_seqlens[b] + j whether or not cache_leftpad is given; rotary tables without k / v are ignored
+    (rotary "only applicable if k and v are passed in").  num_splits is accepted and ignored: it is a scheduling hint (split-K)
+    in flash-attn, and the kernel form is chosen by the library.  bf16 only; head_dim 64, 80 or 128; no sliding window, softcap
+    or alibi; a paged cache takes neither cache_batch_idx nor cache_leftpad (flash-attn refuses both).  All of these are
+    refused before any device work.  A row whose cache_seqlens + s_new exceeds its capacity gets an unspecified result but
+    no access outside the cache (the check needs device values, so the kernel makes it)."""
+    if tuple(window_size) != (-1, -1):
+        raise NotImplementedError("sliding-window attention is not supported")
+    if softcap:
+        raise NotImplementedError("softcap is not supported")
+    if alibi_slopes is not None:
+        raise NotImplementedError("alibi is not supported")
+    if block_table is not None and (cache_batch_idx is not None or cache_leftpad is not None):
+        raise NotImplementedError("a paged KV cache (block_table) supports neither cache_batch_idx nor cache_leftpad")
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("k", k), ("v", v)):
+        if t is not None and t.dtype != torch.bfloat16:
+            raise TypeError(f"flash_attn_with_kvcache supports bfloat16 only ({name} is {t.dtype})")
+    if q.shape[-1] not in _KVCACHE_HEAD_DIMS or k_cache.shape[-1] != q.shape[-1]:
+        raise NotImplementedError(f"head_dim {q.shape[-1]} (cache {k_cache.shape[-1]}): the kernel takes {_KVCACHE_HEAD_DIMS}")
+    if q.shape[2] % k_cache.shape[2]:
+        raise ValueError(f"{q.shape[2]} query heads are not a multiple of {k_cache.shape[2]} kv heads")
+    if (k is None) != (v is None):
+        raise ValueError("give k and v together")
+    as_i32 = lambda t: t if t is None or t.dtype == torch.int32 else t.to(torch.int32)  # noqa: E731
+    if isinstance(cache_seqlens, torch.Tensor):
+        cache_seqlens = as_i32(cache_seqlens).contiguous()
+    return ops.kvcache_attn(q, k_cache, v_cache, k=k, v=v, rotary_cos=rotary_cos, rotary_sin=rotary_sin, cache_seqlens=cache_seqlens,
+                            cache_batch_idx=as_i32(cache_batch_idx), cache_leftpad=as_i32(cache_leftpad), block_table=as_i32(block_table),
+                            softmax_scale=softmax_scale, causal=bool(causal), rotary_interleaved=bool(rotary_interleaved),
+                            return_softmax_lse=bool(return_softmax_lse))
 
 
 # ---- flash_attn.bert_padding ----------------------------------------------------------------------------------------

@@ -840,10 +840,92 @@ def paged_attn(q, k_cache, v_cache, cu_seqlens_q: torch.Tensor, seqlens_k: torch
     return out
 
 
+def _strides3(t: torch.Tensor, name: str):
+    """[B, S, H, d] with unit feature stride -> (batch, row, head) strides in elements."""
+    if t.dim() != 4 or t.stride(3) != 1:
+        raise ValueError(f"{name} must be [batch, seqlen, heads, head_dim] with contiguous features, got {tuple(t.shape)} "
+                         f"strides {t.stride()}")
+    return t.stride(0), t.stride(1), t.stride(2)
+
+
+def kvcache_attn(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None, cache_batch_idx=None,
+                 cache_leftpad=None, block_table=None, softmax_scale: Optional[float] = None, causal: bool = False,
+                 rotary_interleaved: bool = True, return_softmax_lse: bool = False, out: Optional[torch.Tensor] = None):
+    """vsel_kvcache_attn_fwd: append k / v into the cache in place, then attention of q over the visible keys.
+    q [B, s_q, Hq, d] bf16 (any batch / row / head strides, contiguous features; never modified); k_cache / v_cache contiguous
+    [B_cache, L_cache, Hkv, d] (block_table None) or paged [n_blocks, page_size, Hkv, d] with block_table int32 [B, max_pages];
+    k / v [B, s_new, Hkv, d] or None; cache_seqlens int32 [B] tensor (read on the device only) or a Python int (None: the whole
+    cache); cache_batch_idx / cache_leftpad int32 [B] (contiguous cache only); rotary_cos / rotary_sin [seqlen_ro, rotary_dim / 2]
+    (applied with k / v only).  q=None (with out=None): append only.  -> out [B, s_q, Hq, d] (and lse fp32 [B, Hq, s_q])."""
+    dev = _dev(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_seqlens if isinstance(cache_seqlens, torch.Tensor) else None,
+               cache_batch_idx, cache_leftpad, block_table, strided_ok=True)
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache), ("block_table", block_table), ("cache_batch_idx", cache_batch_idx),
+                    ("cache_leftpad", cache_leftpad), ("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("k", k), ("v", v)):
+        if t is not None and t.dtype != torch.bfloat16:
+            raise TypeError(f"kvcache_attn takes bfloat16 tensors ({name} is {t.dtype})")
+    if k_cache.shape != v_cache.shape or k_cache.dim() != 4:
+        raise ValueError("k_cache / v_cache must share one 4-D shape")
+    cache_rows, cache_len, hkv, d = k_cache.shape
+    if q is not None:
+        b, s_q, hq, dq = q.shape
+        qs = _strides3(q, "q")
+    else:
+        if out is not None or return_softmax_lse:
+            raise ValueError("append only (q=None) returns nothing")
+        b, s_q, hq, dq, qs = (k.shape[0] if k is not None else 0), 1, hkv, d, (0, 0, 0)
+    if dq != d:
+        raise ValueError("q and the cache disagree on head_dim")
+    if (k is None) != (v is None):
+        raise ValueError("give k and v together")
+    s_new, ks, vs = 0, (0, 0, 0), (0, 0, 0)
+    if k is not None:
+        if k.shape != v.shape or k.shape[0] != b or k.shape[2] != hkv or k.shape[3] != d:
+            raise ValueError(f"k / v must be [{b}, s_new, {hkv}, {d}], got {tuple(k.shape)} / {tuple(v.shape)}")
+        s_new, ks, vs = k.shape[1], _strides3(k, "k"), _strides3(v, "v")
+    for name, t in (("cache_seqlens", cache_seqlens), ("cache_batch_idx", cache_batch_idx), ("cache_leftpad", cache_leftpad)):
+        if isinstance(t, torch.Tensor) and (t.dtype != torch.int32 or t.numel() != b):
+            raise TypeError(f"{name} must be int32 [{b}]")
+    max_pages = 0
+    if block_table is not None:
+        if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != b:
+            raise TypeError(f"block_table must be int32 [{b}, max_pages]")
+        max_pages = block_table.shape[1]
+    if cache_seqlens is None:
+        cache_seqlens = max_pages * cache_len if block_table is not None else cache_len
+    seqlens_t = cache_seqlens if isinstance(cache_seqlens, torch.Tensor) else None
+    seqlen_scalar = 0 if seqlens_t is not None else int(cache_seqlens)
+    rot = rotary_cos is not None and k is not None
+    if rotary_cos is not None:
+        if rotary_sin is None or rotary_sin.shape != rotary_cos.shape or rotary_cos.dim() != 2 or rotary_cos.dtype != rotary_sin.dtype:
+            raise ValueError("rotary_cos / rotary_sin must be two [seqlen_ro, rotary_dim / 2] tables of one dtype")
+        if rotary_cos.dtype not in (torch.bfloat16, torch.float32):
+            raise TypeError("rotary tables must be bfloat16 or float32")
+    scale = float(softmax_scale) if softmax_scale is not None else d ** -0.5
+    lib = N.lib()
+    if q is not None and out is None:
+        out = torch.empty(b, s_q, hq, d, dtype=torch.bfloat16, device=dev)
+    lse = torch.empty(b * s_q, hq, dtype=torch.float32, device=dev) if return_softmax_lse else None
+    ws = _workspace(lib.vsel_kvcache_attn_workspace_bytes(max(b, 1), s_q, hq, d), dev)
+    if b == 0:
+        return out
+    N.check(lib.vsel_kvcache_attn_fwd(_stream(), _p(q), *qs, k_cache.data_ptr(), v_cache.data_ptr(), cache_rows, cache_len, _p(block_table),
+                                      max_pages, _p(k), _p(v), s_new, *ks, *vs, _p(seqlens_t), seqlen_scalar, _p(cache_batch_idx),
+                                      _p(cache_leftpad), _p(rotary_cos) if rot else None, _p(rotary_sin) if rot else None,
+                                      _code(rotary_cos) if rot else 0, rotary_cos.shape[0] if rot else 0,
+                                      2 * rotary_cos.shape[1] if rot else 0, int(bool(rotary_interleaved)), b, s_q, hq, hkv, d, scale,
+                                      int(bool(causal)), _p(out), _p(lse), ws.data_ptr(), ws.numel()))
+    if return_softmax_lse:
+        return out, lse.view(b, s_q, hq).transpose(1, 2).contiguous()
+    return out
+
+
 # every op that reaches libvsel switches to its tensors' device first
 for _name in ("lis_scores", "lis_select", "lis_select_permuted", "gelu_colsum", "colsum_linear", "lis_select_presummed", "lis_select_varlen",
               "hard_topk", "gather_rows", "soft_topk_fwd", "soft_topk_bwd", "lis_train_fwd", "lis_train_bwd", "lis_train_bwd_factors", "factors_to_grads", "lis_scores_bwd",
               "splice", "splice_batched", "lis_select_splice", "topk_select_splice", "varlen_attn", "varlen_attn_fwd_lse", "varlen_attn_bwd", "varlen_attn_kv",
-              "attn_head_major", "paged_attn"):
+              "attn_head_major", "paged_attn", "kvcache_attn"):
     globals()[_name] = _device_guard(globals()[_name])
 del _name

@@ -7,8 +7,9 @@ qwen-evaluation/token_compression/selector_model.py:270).  Here B prompts are se
   emits cu_seqlens')  ->  the LLM over the packed compressed sequence with var-len attention over cu_seqlens'
   (the packing of qwen-vl-finetune/qwenvl/train/trainer.py:79-113)  ->  last-token logits per prompt.
 Per prompt this computes exactly what `Qwen2_5_VLForConditionalGeneration_Selector.forward` computes for that prompt alone
-(tests/test_hf_gpu.py::test_packed_prefill_matches_per_prompt_forward).  Prefill only (scoring / first token); data-parallel
-serving shards prompts over ranks (ddp.shard_units), no collective.
+(tests/test_hf_gpu.py::test_packed_prefill_matches_per_prompt_forward).  Prefill only (scoring / first token); generation
+on a paged KV cache continues from the same packed inputs in generate.packed_generate.  Data-parallel serving shards prompts
+over ranks (ddp.shard_units), no collective.
 """
 from __future__ import annotations
 
@@ -27,13 +28,29 @@ def packed_prefill(model, input_ids: Sequence[torch.Tensor], pixel_values: torch
     the batch back to back in prompt order; images_per_prompt[b] images belong to prompt b (0 allowed).
     -> dict(logits [B, vocab] at each prompt's last token, cu_seqlens int32 [B+1] of the compressed packing,
             kept [B] visual tokens kept per prompt, hidden [T', D_llm])."""
-    from transformers.models.qwen2_5_vl import modeling_qwen2_5_vl as hf
-    cfg = model.config
-    visual = model.model.visual if hasattr(model.model, "visual") else model.visual
     lm = model.model.language_model
     if lm.config._attn_implementation not in (ATTN_NAME, ATTN_NAME_PACKED):
         raise RuntimeError("packed_prefill needs the LLM on the vsel var-len attention "
                            f"(config._attn_implementation = {ATTN_NAME_PACKED!r})")
+    p = _packed_inputs(model, input_ids, pixel_values, image_grid_thw, images_per_prompt, budgets)
+    cu, max_len = p["cu_seqlens"], p["max_len"]
+    # 5. the LLM over the packed compressed sequence (var-len attention over cu)
+    hidden = lm(inputs_embeds=p["inputs_embeds"][None], position_ids=p["position_ids"][:, None, :], use_cache=False, cu_seq_lens_q=cu,
+                cu_seq_lens_k=cu, max_length_q=max_len, max_length_k=max_len).last_hidden_state[0]
+    last = cu[1:].to(torch.int64) - 1
+    logits = model.lm_head(hidden[last])
+    return {"logits": logits, "cu_seqlens": cu, "kept": p["kept"], "hidden": hidden, "input_ids": p["input_ids"]}
+
+
+@torch.no_grad()
+def _packed_inputs(model, input_ids: Sequence[torch.Tensor], pixel_values: torch.Tensor, image_grid_thw: torch.Tensor,
+                  images_per_prompt: Sequence[int], budgets: float | None = None):
+    """Steps 1-4 of packed_prefill (tower, M-RoPE positions, ragged LIS, packed splice), shared with generate.packed_generate.
+    -> dict(input_ids [T'], inputs_embeds [T', D], position_ids [3, T'], cu_seqlens int32 [B+1], kept [B], max_len,
+            lengths [B] compressed prompt lengths (host ints))."""
+    from transformers.models.qwen2_5_vl import modeling_qwen2_5_vl as hf
+    cfg = model.config
+    visual = model.model.visual if hasattr(model.model, "visual") else model.visual
     if len(images_per_prompt) != len(input_ids) or sum(images_per_prompt) != image_grid_thw.shape[0]:
         raise ValueError("images_per_prompt must have one entry per prompt and sum to the number of image grids")
     dev = pixel_values.device
@@ -78,10 +95,6 @@ def packed_prefill(model, input_ids: Sequence[torch.Tensor], pixel_values: torch
         out, idx, _ = ops.lis_select_varlen(h.contiguous(), [visual_lens[b] for b in has], [ks[b] for b in has], *params)
         _, new_ids, new_emb, new_pos, cu = ops.splice_batched(ids, emb.contiguous(), cfg.image_token_id, seq_lens, visual_lens, ks,
                                                               idx, out.to(emb.dtype), position_ids=pos)
-    # 5. the LLM over the packed compressed sequence (var-len attention over cu)
-    max_len = max(l - n + k for l, n, k in zip(seq_lens, visual_lens, ks))
-    hidden = lm(inputs_embeds=new_emb[None], position_ids=new_pos[:, None, :], use_cache=False, cu_seq_lens_q=cu, cu_seq_lens_k=cu,
-                max_length_q=max_len, max_length_k=max_len).last_hidden_state[0]
-    last = cu[1:].to(torch.int64) - 1
-    logits = model.lm_head(hidden[last])
-    return {"logits": logits, "cu_seqlens": cu, "kept": ks, "hidden": hidden, "input_ids": new_ids}
+    lengths = [l - n + k for l, n, k in zip(seq_lens, visual_lens, ks)]
+    return {"input_ids": new_ids, "inputs_embeds": new_emb, "position_ids": new_pos, "cu_seqlens": cu, "kept": ks,
+            "max_len": max(lengths), "lengths": lengths}
