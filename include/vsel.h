@@ -379,6 +379,18 @@ int vsel_kvcache_attn_fwd(void* stream, const void* q, int64_t q_batch_stride, i
                           int64_t hq, int64_t hkv, int64_t d, float scale, int causal, void* out, float* lse, void* workspace,
                           size_t workspace_bytes);
 
+/* -------- sampling: one token per row of logits (no reference kernel: the reference's eval callers sample through HF generate() with
+ * do_sample = temperature > 0, EV/predict.py:157-159, OV/predict_ov.py:142-144) ----------------------------------------------------
+ * Temperature / top-k / top-p sampling of one token per row (HF warper order).  logits DEVICE [batch, vocab]
+ * bf16 | f32, row_stride in elements; row_ids DEVICE int64 [batch] or NULL (= 0..batch-1); tokens DEVICE int64 [batch]
+ * (-1 for a row with a NaN / +inf or no finite logit); kept DEVICE int32 [batch] or NULL.  VSEL_ERR_INVALID for
+ * temperature <= 0 or not finite, top_p outside (0, 1], top_k < 0, vocab < 1, batch < 0, row_stride < vocab, NULL logits /
+ * tokens -- all checked before any HIP call; VSEL_ERR_UNSUPPORTED for vocab >= 2^24.  A row's token depends only on its own
+ * logits, the parameters, seed, its row id (low 32 bits) and step: not on the batch size, its position or the other rows.       */
+int vsel_sample_tokens(void* stream, const void* logits, vsel_dtype dtype, int64_t batch, int64_t vocab, int64_t row_stride,
+                       float temperature, float top_p, int64_t top_k, uint64_t seed, const int64_t* row_ids, uint64_t step,
+                       int64_t* tokens, int32_t* kept);
+
 /* -------- the same forward with a caller workspace: key-range parts for ONE long sequence ------------------------
  * vsel_varlen_attn_fwd (and _lse when lse != NULL) on batches the launch cannot balance as they are -- one uncompressed prompt, or a
  * few of equal length: 256-query items cut over key ranges, fp32 partial outputs + (m, l) in `ws`, merged in part order by a second

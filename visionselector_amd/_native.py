@@ -28,7 +28,7 @@ class Scorer(C.Structure):
 
 
 # name -> (restype, argtypes); must list every symbol include/vsel.h declares (tests check this)
-_P, _I64, _F, _SZ = C.c_void_p, C.c_int64, C.c_float, C.c_size_t
+_P, _I64, _U64, _F, _SZ = C.c_void_p, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
 _SEG, _SC = C.POINTER(Segments), C.POINTER(Scorer)
 SIGNATURES = {
     "vsel_version": (C.c_char_p, []),
@@ -77,6 +77,7 @@ SIGNATURES = {
     "vsel_kvcache_attn_fwd": (C.c_int, [_P, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64,
                                         _I64, _P, _I64, _P, _P, _P, _P, C.c_int, _I64, _I64, C.c_int, _I64, _I64, _I64, _I64, _I64, _F,
                                         C.c_int, _P, _P, _P, _SZ]),
+    "vsel_sample_tokens": (C.c_int, [_P, _P, C.c_int, _I64, _I64, _I64, _F, _F, _I64, _U64, _P, _U64, _P, _P]),
 }
 
 # include/vsel_debug.h (diagnostic knobs; not part of the drop-in boundary)

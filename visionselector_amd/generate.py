@@ -1,4 +1,4 @@
-"""Batched greedy generation of compressed prompts on a paged KV cache (Qwen2.5-VL selector models).
+"""Batched generation (greedy or sampled) of compressed prompts on a paged KV cache (Qwen2.5-VL selector models).
 
 packed_prefill stops at the first token.  packed_generate continues from the same packed inputs (packed._packed_inputs: tower,
 M-RoPE positions, ragged LIS, splice) and decodes every prompt of the batch together:
@@ -9,8 +9,8 @@ M-RoPE positions, ragged LIS, splice) and decodes every prompt of the batch toge
 The attention interface `vsel_paged` (register_paged_attention) reads the layer's pools through `module.layer_idx` and the
 paged state from the `vsel_paged` keyword argument of the LLM forward -- the route packed_prefill uses for cu_seq_lens_q.
 Page allocation is host bookkeeping: lengths are known from the kept-token counts and the step count, so nothing reads device
-memory except the greedy argmax (one synchronisation per step, as in HF generate).  A prompt that emits eos or reaches
-max_new_tokens leaves the batch and its pages return to the free list.
+memory except the next tokens -- the greedy argmax, or with do_sample ops.sample_tokens (one synchronisation per step, as in HF
+generate).  A prompt that emits eos or reaches max_new_tokens leaves the batch and its pages return to the free list.
 """
 from __future__ import annotations
 
@@ -110,15 +110,24 @@ def _cdiv(a: int, b: int) -> int:
 @torch.no_grad()
 def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torch.Tensor, image_grid_thw: torch.Tensor,
                     images_per_prompt: Sequence[int], max_new_tokens: int, budgets: float | None = None, eos_token_id=None,
-                    page_size: int = 64, pool: PagedKVPool | None = None, return_logits: bool = False):
-    """Greedy generation for a batch of image prompts (arguments as packed_prefill).
+                    page_size: int = 64, pool: PagedKVPool | None = None, return_logits: bool = False, do_sample: bool = False,
+                    temperature: float = 1.0, top_p: float = 1.0, top_k: int = 0, seed: int = 0):
+    """Greedy or sampled generation for a batch of image prompts (arguments as packed_prefill).
     -> dict(tokens: B lists of new token ids (each ends at eos or after max_new_tokens), kept [B], first_logits [B, vocab]
             (bit-identical to packed_prefill's logits), pool, and with return_logits: logits, B lists of [vocab] per step).
     Decode positions continue each prompt's M-RoPE positions from its last prompt token (+1 per step), which is what the batch-1
     Qwen2_5_VLForConditionalGeneration_Selector.generate() uses ("decode positions").
-    pool: a PagedKVPool to draw pages from (default: one sized for this call); every page drawn is back on its free list on return."""
+    pool: a PagedKVPool to draw pages from (default: one sized for this call); every page drawn is back on its free list on return.
+    do_sample=False: the next token is the argmax of the logits.  do_sample=True: ops.sample_tokens with temperature, top_k (0: off),
+    top_p and seed, as HF's do_sample with those warpers; the draw of prompt b at its s-th new token uses row id b and
+    step s, so it does not depend on the other prompts or on when they leave the batch.  A prompt whose logits hold a NaN / +inf
+    (or no finite value) raises RuntimeError."""
     if max_new_tokens < 1:
         raise ValueError("max_new_tokens must be >= 1")
+    if not isinstance(do_sample, bool):
+        raise TypeError(f"do_sample must be a bool, got {do_sample!r}")
+    if do_sample:
+        ops.check_sampling_args(temperature, top_p, top_k, seed)
     eos = set() if eos_token_id is None else ({int(eos_token_id)} if isinstance(eos_token_id, int) else {int(e) for e in eos_token_id})
     lm = model.model.language_model
     register_paged_attention()
@@ -161,12 +170,19 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
         step_logits = [[] for _ in range(n)]
         seqlens = _h2d(lens, torch.int32, dev)
         embed = model.get_input_embeddings()
+        row_ids = torch.arange(n, dtype=torch.int64, device=dev) if do_sample else None     # the prompt index of each active row
         state.mode = "decode"
+        step = 0
         while True:
-            nxt = logits.argmax(-1)
+            if do_sample:
+                nxt = ops.sample_tokens(logits, temperature, top_p, top_k, seed, row_ids=row_ids, step=step)
+            else:
+                nxt = logits.argmax(-1)
             host = nxt.tolist()                                       # the one host synchronisation of a step
             keep = []
             for i, b in enumerate(active):
+                if host[i] < 0:
+                    raise RuntimeError(f"sampling failed for prompt {b} at step {step}: its logits hold a NaN / +inf or no finite value")
                 tokens[b].append(host[i])
                 if return_logits:
                     step_logits[b].append(logits[i])
@@ -180,6 +196,8 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
             if len(keep) < len(active):
                 idx = _h2d(keep, torch.int64, dev)
                 nxt, bt, step_pos, seqlens = nxt[idx], bt[idx], step_pos[:, idx], seqlens[idx]
+                if do_sample:
+                    row_ids = row_ids[idx]
                 active = [active[i] for i in keep]
             for i, b in enumerate(active):                            # this step appends position lens[b]
                 need = _cdiv(lens[b] + 1, page_size)
@@ -194,6 +212,7 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
                 lens[b] += 1
             seqlens = seqlens + 1
             step_pos = step_pos + 1
+            step += 1
     finally:
         lm.config._attn_implementation = old_impl
         for pg in pages:

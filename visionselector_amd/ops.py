@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import itertools
+import math
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -922,10 +923,54 @@ def kvcache_attn(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_si
     return out
 
 
+def check_sampling_args(temperature, top_p, top_k, seed) -> Tuple[float, float, int, int]:
+    """Host checks of the sampling parameters (vsel_sample_tokens takes temperature / top_p as float32): temperature finite and > 0,
+    top_p in (0, 1], top_k an int >= 0 (0: no top-k filter), seed an int in [0, 2^64).  -> the values as passed to the library."""
+    t, p = C.c_float(float(temperature)).value, C.c_float(float(top_p)).value
+    if not (math.isfinite(t) and t > 0):
+        raise ValueError(f"temperature must be finite and > 0 (as float32), got {temperature!r}")
+    if not (0.0 < float(top_p) <= 1.0 and p > 0):
+        raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
+        raise ValueError(f"top_k must be an int >= 0, got {top_k!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be an int in [0, 2^64), got {seed!r}")
+    return t, p, top_k, seed
+
+
+def sample_tokens(logits: torch.Tensor, temperature: float, top_p: float = 1.0, top_k: int = 0, seed: int = 0,
+                  row_ids: Optional[torch.Tensor] = None, step: int = 0, return_kept: bool = False):
+    """vsel_sample_tokens: one token per row of logits [B, V] (bf16 / fp32, any row stride, contiguous columns) by temperature,
+    top-k (0: off), then top-p, as HF's warper chain orders them.  row_ids int64 [B] on the device (default
+    0..B-1; low 32 bits used) and step pick the random stream: a row's draw depends only on its logits, the parameters, seed,
+    its row id and step.  No host synchronisation.  -> int64 [B] (-1 for a row with a NaN / +inf or no finite logit), and with
+    return_kept also int32 [B], the size of each row's kept set."""
+    dev = _dev(logits, row_ids, strided_ok=True)
+    if logits.dim() != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError(f"logits must be [batch, vocab] with contiguous columns, got {tuple(logits.shape)} strides {logits.stride()}")
+    code = _code(logits)
+    t, p, top_k, seed = check_sampling_args(temperature, top_p, top_k, seed)
+    if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
+        raise ValueError(f"step must be an int in [0, 2^64), got {step!r}")
+    b, v = logits.shape
+    if v < 1:
+        raise ValueError("empty vocabulary")
+    if row_ids is not None:
+        if row_ids.dtype != torch.int64 or row_ids.shape != (b,):
+            raise TypeError(f"row_ids must be int64 [{b}]")
+        row_ids = row_ids.contiguous()
+    stride = logits.stride(0) if b > 1 else v
+    tokens = torch.empty(b, dtype=torch.int64, device=dev)
+    kept = torch.empty(b, dtype=torch.int32, device=dev) if return_kept else None
+    N.check(N.lib().vsel_sample_tokens(_stream(), logits.data_ptr(), code, b, v, stride, t, p, top_k, seed, _p(row_ids), step,
+                                       tokens.data_ptr(), _p(kept)))
+    return (tokens, kept) if return_kept else tokens
+
+
 # every op that reaches libvsel switches to its tensors' device first
 for _name in ("lis_scores", "lis_select", "lis_select_permuted", "gelu_colsum", "colsum_linear", "lis_select_presummed", "lis_select_varlen",
               "hard_topk", "gather_rows", "soft_topk_fwd", "soft_topk_bwd", "lis_train_fwd", "lis_train_bwd", "lis_train_bwd_factors", "factors_to_grads", "lis_scores_bwd",
               "splice", "splice_batched", "lis_select_splice", "topk_select_splice", "varlen_attn", "varlen_attn_fwd_lse", "varlen_attn_bwd", "varlen_attn_kv",
-              "attn_head_major", "paged_attn", "kvcache_attn"):
+              "attn_head_major", "paged_attn", "kvcache_attn", "sample_tokens"):
     globals()[_name] = _device_guard(globals()[_name])
 del _name
