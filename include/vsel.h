@@ -391,6 +391,26 @@ int vsel_sample_tokens(void* stream, const void* logits, vsel_dtype dtype, int64
                        float temperature, float top_p, int64_t top_k, uint64_t seed, const int64_t* row_ids, uint64_t step,
                        int64_t* tokens, int32_t* kept);
 
+/* -------- repetition penalty over per-prompt token sets (no reference kernel: HF generate() applies RepetitionPenaltyLogitsProcessor
+ * whenever the merged generation config holds repetition_penalty != 1.0, greedy or sampled; the eval callers leave it to the
+ * checkpoint's generation_config.json) ------------------------------------------------------------------------------------------------
+ * vsel_token_sets_build: sets DEVICE uint32 [n_sets, ceil(vocab / 32)] (overwritten) = one bitset per set of the ragged ids DEVICE int64
+ * (set s: ids[cu[s] .. cu[s+1]), cu DEVICE int64 [n_sets + 1]); ids outside [0, vocab) are skipped.  VSEL_ERR_INVALID for NULL ids / cu /
+ * sets, n_sets < 0, vocab < 1; VSEL_ERR_UNSUPPORTED for vocab >= 2^31.  n_sets == 0 is a no-op.
+ * vsel_repetition_penalty: per row r of logits DEVICE [batch, vocab] bf16 | f32 (row_stride in elements), with the set
+ * s = row_ids[r] (DEVICE int64 [batch], or NULL = r), in fp32 with theta = (float)penalty and inv = (float)(1 / penalty) (the reciprocal
+ * of the double, rounded once): y_i = x_i < 0 ? x_i * theta : x_i * inv for i in set s or i == prev_tokens[r] (DEVICE int64 [batch] or NULL), y_i = x_i otherwise (bit for bit HF's processor on
+ * the GPU).  Outputs, either or both: tokens DEVICE int64 [batch] = argmax(y) as torch.argmax (NaN largest, lowest index among equal
+ * values, +0 == -0); out DEVICE f32 [batch, vocab] contiguous = y.  prev_tokens[r] is added to set s by the launch (ignored outside
+ * [0, vocab)).  Row ids must be DISTINCT within a launch; a row id outside [0, n_sets) reads as the empty set and changes nothing.  One
+ * launch, no workspace, no host synchronisation.  VSEL_ERR_INVALID for penalty <= 0 or not finite (also as float32), vocab < 1, batch < 0,
+ * row_stride < vocab, n_sets < 0, NULL logits / sets, tokens and out both NULL -- all checked before any HIP call;
+ * VSEL_ERR_UNSUPPORTED for vocab >= 2^31.  batch == 0 is a no-op.                                                                   */
+int vsel_token_sets_build(void* stream, const int64_t* ids, const int64_t* cu, int64_t n_sets, int64_t vocab, uint32_t* sets);
+int vsel_repetition_penalty(void* stream, const void* logits, vsel_dtype dtype, int64_t batch, int64_t vocab, int64_t row_stride,
+                            double penalty, uint32_t* sets, int64_t n_sets, const int64_t* row_ids, const int64_t* prev_tokens,
+                            int64_t* tokens, float* out);
+
 /* -------- the same forward with a caller workspace: key-range parts for ONE long sequence ------------------------
  * vsel_varlen_attn_fwd (and _lse when lse != NULL) on batches the launch cannot balance as they are -- one uncompressed prompt, or a
  * few of equal length: 256-query items cut over key ranges, fp32 partial outputs + (m, l) in `ws`, merged in part order by a second

@@ -9,8 +9,10 @@ M-RoPE positions, ragged LIS, splice) and decodes every prompt of the batch toge
 The attention interface `vsel_paged` (register_paged_attention) reads the layer's pools through `module.layer_idx` and the
 paged state from the `vsel_paged` keyword argument of the LLM forward -- the route packed_prefill uses for cu_seq_lens_q.
 Page allocation is host bookkeeping: lengths are known from the kept-token counts and the step count, so nothing reads device
-memory except the next tokens -- the greedy argmax, or with do_sample ops.sample_tokens (one synchronisation per step, as in HF
-generate).  A prompt that emits eos or reaches max_new_tokens leaves the batch and its pages return to the free list.
+memory except the next tokens -- the greedy argmax, or with do_sample ops.sample_tokens, either after ops.repetition_penalty when
+one is set (one synchronisation per step, as in HF generate).  A prompt that emits eos or reaches max_new_tokens leaves the batch and
+its pages return to the free list.  hf_generation_kwargs turns HF generate() keyword arguments and the model's generation_config into
+packed_generate's.
 """
 from __future__ import annotations
 
@@ -111,7 +113,7 @@ def _cdiv(a: int, b: int) -> int:
 def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torch.Tensor, image_grid_thw: torch.Tensor,
                     images_per_prompt: Sequence[int], max_new_tokens: int, budgets: float | None = None, eos_token_id=None,
                     page_size: int = 64, pool: PagedKVPool | None = None, return_logits: bool = False, do_sample: bool = False,
-                    temperature: float = 1.0, top_p: float = 1.0, top_k: int = 0, seed: int = 0):
+                    temperature: float = 1.0, top_p: float = 1.0, top_k: int = 0, seed: int = 0, repetition_penalty: float = 1.0):
     """Greedy or sampled generation for a batch of image prompts (arguments as packed_prefill).
     -> dict(tokens: B lists of new token ids (each ends at eos or after max_new_tokens), kept [B], first_logits [B, vocab]
             (bit-identical to packed_prefill's logits), pool, and with return_logits: logits, B lists of [vocab] per step).
@@ -128,8 +130,11 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
         raise TypeError(f"do_sample must be a bool, got {do_sample!r}")
     if do_sample:
         ops.check_sampling_args(temperature, top_p, top_k, seed)
+    penalize = ops.check_repetition_penalty(repetition_penalty) != 1.0
     eos = set() if eos_token_id is None else ({int(eos_token_id)} if isinstance(eos_token_id, int) else {int(e) for e in eos_token_id})
     lm = model.model.language_model
+    # the token sets of the penalty: every prompt id as passed (range-checked on the host before any device work)
+    sets = ops.token_sets(input_ids, model.lm_head.out_features, model.lm_head.weight.device) if penalize else None
     register_paged_attention()
     p = _packed_inputs(model, input_ids, pixel_values, image_grid_thw, images_per_prompt, budgets)
     emb, pos, cu, lengths = p["inputs_embeds"], p["position_ids"], p["cu_seqlens"], p["lengths"]
@@ -170,11 +175,18 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
         step_logits = [[] for _ in range(n)]
         seqlens = _h2d(lens, torch.int32, dev)
         embed = model.get_input_embeddings()
-        row_ids = torch.arange(n, dtype=torch.int64, device=dev) if do_sample else None     # the prompt index of each active row
+        # the prompt index of each active row (the sampler's row id, the penalty's token set)
+        row_ids = torch.arange(n, dtype=torch.int64, device=dev) if do_sample or penalize else None
+        prev = None                                                   # the last step's tokens, which join the sets at this step
         state.mode = "decode"
         step = 0
         while True:
-            if do_sample:
+            if penalize and do_sample:
+                pen = ops.repetition_penalty(logits, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prev)
+                nxt = ops.sample_tokens(pen, temperature, top_p, top_k, seed, row_ids=row_ids, step=step)
+            elif penalize:
+                nxt = ops.repetition_penalty(logits, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prev, return_tokens=True)
+            elif do_sample:
                 nxt = ops.sample_tokens(logits, temperature, top_p, top_k, seed, row_ids=row_ids, step=step)
             else:
                 nxt = logits.argmax(-1)
@@ -196,7 +208,7 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
             if len(keep) < len(active):
                 idx = _h2d(keep, torch.int64, dev)
                 nxt, bt, step_pos, seqlens = nxt[idx], bt[idx], step_pos[:, idx], seqlens[idx]
-                if do_sample:
+                if row_ids is not None:
                     row_ids = row_ids[idx]
                 active = [active[i] for i in keep]
             for i, b in enumerate(active):                            # this step appends position lens[b]
@@ -204,6 +216,7 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
                 if need > len(pages[b]):
                     pages[b] += pool.alloc(1)
                     bt[i, need - 1] = pages[b][-1]
+            prev = nxt
             state.block_table, state.cache_seqlens = bt, seqlens
             hidden = lm(inputs_embeds=embed(nxt)[None], position_ids=step_pos[:, None, :], use_cache=False,
                         vsel_paged=state).last_hidden_state[0]
@@ -221,3 +234,60 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
     if return_logits:
         out["logits"] = step_logits
     return out
+
+
+# HF generation options packed_generate cannot honour, each with the condition under which HF's _get_logits_processor (or its search
+# loop) makes it active: hf_generation_kwargs refuses them by name instead of returning kwargs that would generate something else
+_UNSUPPORTED = (
+    ("num_beams", lambda g: g.num_beams is not None and g.num_beams > 1),
+    ("num_return_sequences", lambda g: g.num_return_sequences is not None and g.num_return_sequences > 1),
+    ("guidance_scale", lambda g: g.guidance_scale is not None and g.guidance_scale != 1),
+    ("sequence_bias", lambda g: g.sequence_bias is not None),
+    ("encoder_repetition_penalty", lambda g: g.encoder_repetition_penalty is not None and g.encoder_repetition_penalty != 1.0),
+    ("no_repeat_ngram_size", lambda g: g.no_repeat_ngram_size is not None and g.no_repeat_ngram_size > 0),
+    ("encoder_no_repeat_ngram_size", lambda g: g.encoder_no_repeat_ngram_size is not None and g.encoder_no_repeat_ngram_size > 0),
+    ("bad_words_ids", lambda g: g.bad_words_ids is not None),
+    ("min_length", lambda g: g.min_length is not None and g.min_length > 0),
+    ("min_new_tokens", lambda g: g.min_new_tokens is not None and g.min_new_tokens > 0),
+    ("forced_bos_token_id", lambda g: g.forced_bos_token_id is not None),
+    ("forced_eos_token_id", lambda g: g.forced_eos_token_id is not None),
+    ("remove_invalid_values", lambda g: g.remove_invalid_values is True),
+    ("exponential_decay_length_penalty", lambda g: g.exponential_decay_length_penalty is not None),
+    ("suppress_tokens", lambda g: g.suppress_tokens is not None),
+    ("begin_suppress_tokens", lambda g: g.begin_suppress_tokens is not None),
+    ("watermarking_config", lambda g: getattr(g, "watermarking_config", None) is not None),
+    ("renormalize_logits", lambda g: g.renormalize_logits is True),
+    ("stop_strings", lambda g: getattr(g, "stop_strings", None) is not None),
+    ("max_time", lambda g: getattr(g, "max_time", None) is not None),
+    # the warpers HF applies only when sampling
+    ("top_h", lambda g: g.do_sample and getattr(g, "top_h", None) is not None),
+    ("min_p", lambda g: g.do_sample and g.min_p is not None),
+    ("typical_p", lambda g: g.do_sample and g.typical_p is not None and g.typical_p < 1.0),
+    ("epsilon_cutoff", lambda g: g.do_sample and g.epsilon_cutoff is not None and 0.0 < g.epsilon_cutoff < 1.0),
+    ("eta_cutoff", lambda g: g.do_sample and g.eta_cutoff is not None and 0.0 < g.eta_cutoff < 1.0),
+)
+
+
+def hf_generation_kwargs(model, **generate_kwargs) -> dict:
+    """The packed_generate keyword arguments that reproduce HF `model.generate(**generate_kwargs)`: transformers' own merge
+    (GenerationMixin._prepare_generation_config: the caller's kwargs over model.generation_config over HF's global defaults, e.g.
+    top_k 50) -> dict(do_sample, temperature, top_p, top_k, repetition_penalty, eos_token_id, max_new_tokens), with HF's "off" values
+    as packed_generate spells them (top_p 1.0, top_k 0, repetition_penalty 1.0).  NotImplementedError, naming the option, for any
+    active setting packed_generate does not implement (beam search, min-p, n-gram blocking, ..., max_length without max_new_tokens): the
+    caller then runs HF generate() itself rather than getting other answers.  TypeError for keywords that are no generation option.
+    `seed` is not HF's: pass it to packed_generate directly."""
+    g, rest = model._prepare_generation_config(None, **generate_kwargs)
+    rest = {k: v for k, v in rest.items() if k not in ("output_attentions", "output_hidden_states")}     # (outputs, not tokens)
+    if rest:
+        raise TypeError(f"not generation options: {sorted(rest)}")
+    for name, active in _UNSUPPORTED:
+        if active(g):
+            raise NotImplementedError(f"packed_generate does not implement the generation option {name}={getattr(g, name)!r}; "
+                                      "use the model's generate()")
+    if g.max_new_tokens is None:
+        raise NotImplementedError(f"packed_generate needs max_new_tokens (the merged config gives max_length={g.max_length!r} "
+                                  "without it); use the model's generate() or pass max_new_tokens")
+    return dict(do_sample=bool(g.do_sample), temperature=1.0 if g.temperature is None else float(g.temperature),
+                top_p=1.0 if g.top_p is None else float(g.top_p), top_k=0 if g.top_k is None else int(g.top_k),
+                repetition_penalty=1.0 if g.repetition_penalty is None else float(g.repetition_penalty),
+                eos_token_id=g.eos_token_id, max_new_tokens=int(g.max_new_tokens))

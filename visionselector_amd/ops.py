@@ -967,10 +967,85 @@ def sample_tokens(logits: torch.Tensor, temperature: float, top_p: float = 1.0, 
     return (tokens, kept) if return_kept else tokens
 
 
+def check_repetition_penalty(penalty) -> float:
+    """Host check of a repetition penalty as HF's RepetitionPenaltyLogitsProcessor takes it: a number > 0, here also finite (and > 0 as
+    the float32 the library computes with).  -> float(penalty)."""
+    if isinstance(penalty, bool) or not isinstance(penalty, (int, float)):
+        raise ValueError(f"repetition_penalty must be a float > 0, got {penalty!r}")
+    p = float(penalty)
+    if not (math.isfinite(p) and p > 0 and C.c_float(p).value > 0):
+        raise ValueError(f"repetition_penalty must be a finite float > 0, got {penalty!r}")
+    return p
+
+
+def token_sets(ids_list, vocab: int, device) -> torch.Tensor:
+    """vsel_token_sets_build: one bitset of ceil(vocab / 32) uint32 words (held as int32) per entry of ids_list (1-D int tensors on any
+    device, or int sequences; duplicates count once) -> int32 [len(ids_list), ceil(vocab / 32)] on `device`, for repetition_penalty.
+    Ids outside [0, vocab) raise ValueError before any device work."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("visionselector_amd ops run on the GPU only (HIP kernels in libvsel.so); "
+                           f"got device {dev}.  There is no CPU fallback.")
+    vocab = int(vocab)
+    if not 1 <= vocab < 2 ** 31:
+        raise ValueError(f"vocab must be in [1, 2^31), got {vocab}")
+    host = [torch.as_tensor(x).detach().to("cpu", torch.int64).reshape(-1) for x in ids_list]
+    for s, h in enumerate(host):
+        if h.numel() and (int(h.min()) < 0 or int(h.max()) >= vocab):
+            raise ValueError(f"token set {s}: ids must be in [0, {vocab}), got min {int(h.min())} max {int(h.max())}")
+    n = len(host)
+    cu = [0]
+    for h in host:
+        cu.append(cu[-1] + h.numel())
+    ids = torch.cat(host) if cu[-1] else torch.zeros(1, dtype=torch.int64)            # (never read when every set is empty)
+    with torch.cuda.device(dev):
+        sets = torch.empty(n, (vocab + 31) // 32, dtype=torch.int32, device=dev)
+        if n == 0:
+            return sets
+        ids_d = ids.pin_memory().to(dev, non_blocking=True)
+        cu_d = torch.tensor(cu, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        N.check(N.lib().vsel_token_sets_build(_stream(), ids_d.data_ptr(), cu_d.data_ptr(), n, vocab, sets.data_ptr()))
+    return sets
+
+
+def repetition_penalty(logits: torch.Tensor, penalty: float, sets: torch.Tensor, row_ids: Optional[torch.Tensor] = None,
+                       prev_tokens: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, return_tokens: bool = False):
+    """vsel_repetition_penalty: HF's RepetitionPenaltyLogitsProcessor on logits [B, V] (bf16 / fp32, any row stride, contiguous columns)
+    in fp32, row b penalising the ids of sets[row_ids[b]] (token_sets; row_ids int64 [B] on the device, default 0..B-1, DISTINCT) and
+    prev_tokens[b] (int64 [B] or None), which the launch then adds to that set.  No host synchronisation.
+    -> y fp32 [B, V] (written into `out` when given); return_tokens=True: the greedy tokens int64 [B] = argmax(y) instead, without an fp32
+    row unless `out` is given too, then (out, tokens)."""
+    dev = _dev(logits, sets, row_ids, prev_tokens, out, strided_ok=True)
+    if logits.dim() != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError(f"logits must be [batch, vocab] with contiguous columns, got {tuple(logits.shape)} strides {logits.stride()}")
+    code = _code(logits)
+    p = check_repetition_penalty(penalty)
+    b, v = logits.shape
+    if v < 1:
+        raise ValueError("empty vocabulary")
+    if sets.dtype != torch.int32 or sets.dim() != 2 or sets.shape[1] != (v + 31) // 32 or not sets.is_contiguous():
+        raise ValueError(f"sets must be contiguous int32 [n_sets, {(v + 31) // 32}] (token_sets for vocab {v}), got {sets.dtype} "
+                         f"{tuple(sets.shape)}")
+    for name, t in (("row_ids", row_ids), ("prev_tokens", prev_tokens)):
+        if t is not None and (t.dtype != torch.int64 or t.shape != (b,) or not t.is_contiguous()):
+            raise TypeError(f"{name} must be contiguous int64 [{b}]")
+    if out is not None and (out.dtype != torch.float32 or out.shape != (b, v) or not out.is_contiguous()):
+        raise ValueError(f"out must be contiguous float32 [{b}, {v}]")
+    if out is None and not return_tokens:
+        out = torch.empty(b, v, dtype=torch.float32, device=dev)
+    tokens = torch.empty(b, dtype=torch.int64, device=dev) if return_tokens else None
+    stride = logits.stride(0) if b > 1 else v
+    N.check(N.lib().vsel_repetition_penalty(_stream(), logits.data_ptr(), code, b, v, stride, p, sets.data_ptr(), sets.shape[0],
+                                            _p(row_ids), _p(prev_tokens), _p(tokens), _p(out)))
+    if not return_tokens:
+        return out
+    return tokens if out is None else (out, tokens)
+
+
 # every op that reaches libvsel switches to its tensors' device first
 for _name in ("lis_scores", "lis_select", "lis_select_permuted", "gelu_colsum", "colsum_linear", "lis_select_presummed", "lis_select_varlen",
               "hard_topk", "gather_rows", "soft_topk_fwd", "soft_topk_bwd", "lis_train_fwd", "lis_train_bwd", "lis_train_bwd_factors", "factors_to_grads", "lis_scores_bwd",
               "splice", "splice_batched", "lis_select_splice", "topk_select_splice", "varlen_attn", "varlen_attn_fwd_lse", "varlen_attn_bwd", "varlen_attn_kv",
-              "attn_head_major", "paged_attn", "kvcache_attn", "sample_tokens"):
+              "attn_head_major", "paged_attn", "kvcache_attn", "sample_tokens", "token_sets", "repetition_penalty"):
     globals()[_name] = _device_guard(globals()[_name])
 del _name
