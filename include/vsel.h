@@ -411,6 +411,24 @@ int vsel_repetition_penalty(void* stream, const void* logits, vsel_dtype dtype, 
                             double penalty, uint32_t* sets, int64_t n_sets, const int64_t* row_ids, const int64_t* prev_tokens,
                             int64_t* tokens, float* out);
 
+/* -------- decode-step bookkeeping on the device (no reference kernel: HF generate() keeps finished flags and lengths in torch tensors
+ * and reads them on the host every step; this launch is what lets packed_generate(graph=True) replay the LLM step from a captured graph
+ * without reading a token on the host) ----------------------------------------------------------------------------------
+ * vsel_decode_advance: one launch after the step's selector.  next DEVICE int64 [batch] (argmax, vsel_sample_tokens or
+ * vsel_repetition_penalty); eos DEVICE int64 [n_eos] (NULL when n_eos == 0).  State, updated in place: done int32 [batch] (0 active,
+ * 1 eos, 2 length, 3 invalid logits), n_tokens int32 [batch], cache_seqlens int32 [batch], pos [3, batch] int32 (pos_is_int64 0) or
+ * int64 (1), feed int64 [batch], tokens_out int64 [batch, max_new_tokens], status int32 [4] (overwritten) = {rows active after the
+ * launch, lowest row that turned invalid in it or -1, that row's n_tokens or -1, 0}.  A row with done != 0 on entry changes nothing.
+ * An active row: n_tokens > 0 on entry -> cache_seqlens += 1, pos += 1; then t = next[b]: t < 0 -> done = 3; else
+ * tokens_out[b, n_tokens] = t, n_tokens += 1, and done = 1 if t is in eos, else done = 2 if n_tokens == max_new_tokens, else
+ * feed[b] = t.  An active row with n_tokens outside [0, max_new_tokens) gets done = 2 and nothing else.  One workgroup, no workspace,
+ * no host synchronisation, capturable.  VSEL_ERR_INVALID for a NULL pointer (eos only with n_eos > 0), batch < 0, n_eos < 0,
+ * max_new_tokens < 1, pos_is_int64 not 0 / 1 -- all checked before any HIP call; VSEL_ERR_UNSUPPORTED for batch or max_new_tokens
+ * >= 2^31.  batch == 0 writes status {0, -1, -1, 0}.                                                                              */
+int vsel_decode_advance(void* stream, const int64_t* next, int64_t batch, const int64_t* eos, int64_t n_eos, int64_t max_new_tokens,
+                        int32_t* done, int32_t* n_tokens, int32_t* cache_seqlens, void* pos, int pos_is_int64, int64_t* feed,
+                        int64_t* tokens_out, int32_t* status);
+
 /* -------- the same forward with a caller workspace: key-range parts for ONE long sequence ------------------------
  * vsel_varlen_attn_fwd (and _lse when lse != NULL) on batches the launch cannot balance as they are -- one uncompressed prompt, or a
  * few of equal length: 256-query items cut over key ranges, fp32 partial outputs + (m, l) in `ws`, merged in part order by a second

@@ -1,6 +1,6 @@
 """Decode on a KV cache: flash_attn_with_kvcache at kernel level, packed_generate at model level.  One JSON line per measurement.
 
-    python tools/bench_generate.py [--kernel] [--model] [--batches 1,8,32] [--new-tokens 64]
+    python tools/bench_generate.py [--kernel] [--model] [--graph] [--batches 1,8,32] [--new-tokens 64] [--repeats 3] [--lookaheads 1,2,4,8]
 
 Kernel level (7B heads: 28 q / 4 kv, d 128, s_q = s_new = 1): B in {1, 8, 32, 64, 256} x cache length in {524, 2368}, three
 layouts -- paged (page 64, scattered pages), contiguous, contiguous with left padding (cache_leftpad + cache_batch_idx) --
@@ -10,6 +10,10 @@ the bytes it moves: the new K / V rows read and written, 2 x 2 x B x Hkv x d x 2
 Model level: a Qwen2.5-VL-7B-geometry selector model with random bf16 weights (built as tools/bench_e2e.py builds it), B prompts
 of 2304 visual tokens + 64 text tokens, budget 0.2, N new tokens: packed_generate tokens/s against B sequential batch-1
 model.generate() calls (greedy, min_new_tokens = max_new_tokens so that both produce the same count).
+--graph: the same model and prompts, packed_generate(graph=False) against packed_generate(graph=DecodeGraphs) in one process,
+alternating, warmed up, best of --repeats each, the captured graphs reused across repeats and the capture time reported apart; then the
+lookahead sweep (graph mode only) at the smallest and the largest batch.  ms per decode step = (best time - best prefill-only time) /
+(new tokens - 1); tok/s counts the whole call, prefill included, as the --model leg does.
 Every line carries the box (host, device) and the commit (VSEL_COMMIT, since the tree may travel without its .git)."""
 import argparse
 import json
@@ -103,12 +107,14 @@ def kernel_level():
             _stamp(rec)
 
 
-def model_level(batches, new_tokens):
+IMG, VID, VSTART, VEND = 151655, 151656, 151652, 151653
+
+
+def _model_and_prompts(n_prompts):
+    """-> (model, prompts, pixel rows per prompt, the one image grid, visual tokens, text tokens)"""
     from transformers import Qwen2_5_VLConfig
     from visionselector_amd.attention import ATTN_NAME, ATTN_NAME_PACKED, replace_qwen2_vl_attention_class
-    from visionselector_amd.generate import packed_generate
     from visionselector_amd.hf_qwen25vl import Qwen2_5_VLForConditionalGeneration_Selector
-    IMG, VID, VSTART, VEND = 151655, 151656, 151652, 151653
     replace_qwen2_vl_attention_class()
     cfg = Qwen2_5_VLConfig(
         text_config=dict(hidden_size=3584, intermediate_size=18944, num_hidden_layers=28, num_attention_heads=28,
@@ -132,12 +138,18 @@ def model_level(batches, new_tokens):
     grid, n_vis, n_text = (1, 96, 96), 96 * 96 // 4, 64
     g = torch.Generator().manual_seed(1)
     prompts, pix = [], []
-    for _ in range(max(batches)):
+    for _ in range(n_prompts):
         pre = torch.randint(1000, 5000, (n_text // 2,), generator=g)
         post = torch.randint(1000, 5000, (n_text - n_text // 2 - 2,), generator=g)
         prompts.append(torch.cat((pre, torch.tensor([VSTART]), torch.full((n_vis,), IMG), torch.tensor([VEND]), post)))
         pix.append(torch.randn(96 * 96, 3 * 2 * 14 * 14, generator=g).bfloat16())
     grid_t = torch.tensor([list(grid)]).cuda()
+    return model, prompts, pix, grid_t, n_vis, n_text
+
+
+def model_level(batches, new_tokens):
+    from visionselector_amd.generate import packed_generate
+    model, prompts, pix, grid_t, n_vis, n_text = _model_and_prompts(max(batches))
 
     def packed(b, n=new_tokens):
         out = packed_generate(model, prompts[:b], torch.cat(pix[:b]).cuda(), grid_t.repeat(b, 1), [1] * b, max_new_tokens=n)
@@ -168,16 +180,73 @@ def model_level(batches, new_tokens):
         _stamp(res)
 
 
+def graph_level(batches, new_tokens, repeats, lookaheads):
+    from visionselector_amd.generate import DEFAULT_LOOKAHEAD, DecodeGraphs, PagedKVPool, packed_generate
+    model, prompts, pix, grid_t, n_vis, n_text = _model_and_prompts(max(batches))
+    lm = model.model.language_model
+    length = n_text + max(1, int(n_vis * 0.2))
+    width = -(-(length + new_tokens - 1) // PAGE)
+    pool = PagedKVPool(len(lm.layers), max(batches) * width, PAGE, HKV, D, "cuda")
+    graphs = DecodeGraphs(model, pool, width)
+
+    def run(b, n=new_tokens, **kw):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = packed_generate(model, prompts[:b], torch.cat(pix[:b]).cuda(), grid_t.repeat(b, 1), [1] * b, max_new_tokens=n, pool=pool, **kw)
+        torch.cuda.synchronize()
+        assert all(len(t) == n for t in out["tokens"])
+        return time.perf_counter() - t0, out["tokens"]
+
+    def line(b, best, prefill):
+        return {"s": round(best, 4), "tok_per_s": round(b * new_tokens / best, 1),
+                "ms_per_decode_step": round((best - prefill) / (new_tokens - 1) * 1e3, 3)}
+
+    for b in batches:
+        run(b, 2)                   # warm-up at this batch's shapes (the tower's first call at a new image count costs seconds)
+        before = graphs.capture_ms
+        run(b, 2, graph=graphs)     # captures this batch's graph
+        res = {"bench": "packed_generate_graph", "batch": b, "visual_tokens": n_vis, "text_tokens": n_text, "budget": 0.2,
+               "new_tokens": new_tokens, "repeats": repeats, "lookahead": DEFAULT_LOOKAHEAD, "model": "Qwen2.5-VL-7B geometry, random-init bf16",
+               "capture_ms": round(graphs.capture_ms - before, 1)}
+        prefill = min(run(b, 1)[0] for _ in range(repeats))
+        best = {"eager": float("inf"), "graph": float("inf")}
+        for _ in range(repeats):     # alternating
+            for tag, kw in (("eager", dict()), ("graph", dict(graph=graphs))):
+                s, toks = run(b, **kw)
+                best[tag] = min(best[tag], s)
+                res.setdefault("tokens_equal", True)
+                if tag == "eager":
+                    ref = toks
+                elif toks != ref:
+                    res["tokens_equal"] = False
+        res["prefill_only_s"] = round(prefill, 4)
+        res["eager"], res["graph"] = line(b, best["eager"], prefill), line(b, best["graph"], prefill)
+        res["graph_vs_eager"] = round(best["eager"] / best["graph"], 3)
+        res["captures"] = graphs.captures
+        _stamp(res)
+    for b in sorted({batches[0], batches[-1]}) if lookaheads else ():
+        res = {"bench": "packed_generate_graph_lookahead", "batch": b, "new_tokens": new_tokens, "repeats": repeats}
+        prefill = min(run(b, 1)[0] for _ in range(repeats))
+        for la in lookaheads:
+            res[f"lookahead_{la}"] = line(b, min(run(b, graph=graphs, lookahead=la)[0] for _ in range(repeats)), prefill)
+        _stamp(res)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernel", action="store_true")
     ap.add_argument("--model", action="store_true")
+    ap.add_argument("--graph", action="store_true")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--lookaheads", default="1,2,4,8", help="the sweep of --graph ('' to skip it)")
     ap.add_argument("--batches", default="1,8,32")
     ap.add_argument("--new-tokens", type=int, default=64)
     a = ap.parse_args()
-    if not a.kernel and not a.model:
+    if not a.kernel and not a.model and not a.graph:
         a.kernel = a.model = True
     if a.kernel:
         kernel_level()
     if a.model:
         model_level([int(x) for x in a.batches.split(",")], a.new_tokens)
+    if a.graph:
+        graph_level([int(x) for x in a.batches.split(",")], a.new_tokens, a.repeats, [int(x) for x in a.lookaheads.split(",") if x])

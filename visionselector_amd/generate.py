@@ -13,9 +13,13 @@ memory except the next tokens -- the greedy argmax, or with do_sample ops.sample
 one is set (one synchronisation per step, as in HF generate).  A prompt that emits eos or reaches max_new_tokens leaves the batch and
 its pages return to the free list.  hf_generation_kwargs turns HF generate() keyword arguments and the model's generation_config into
 packed_generate's.
+packed_generate(graph=True) keeps the decode loop on the device: the LLM step is replayed from a captured graph, the
+token bookkeeping is one ops.decode_advance launch per step, and the host reads a four-word status `lookahead` steps behind instead of
+the tokens.  DecodeGraphs keeps the captured graphs between calls.
 """
 from __future__ import annotations
 
+import time
 from typing import Sequence
 
 import torch
@@ -109,11 +113,146 @@ def _cdiv(a: int, b: int) -> int:
     return -(-a // b)
 
 
+DEFAULT_LOOKAHEAD = 2        # steps the host runs ahead of the status it reads (tools/bench_generate.py --graph sweep)
+_INVALID_LOGITS = "its logits hold a NaN / +inf or no finite value"
+
+
+class _StepGraph:
+    """The static buffers of one batch size and, once captured, the graph of the LLM decode step + lm_head over them."""
+
+    def __init__(self, n: int, width: int, pos_dtype, pool: PagedKVPool, dev):
+        # done, n_tokens (int32 [n] each) and feed (int64 [n]) share one buffer: one fill resets a call's state
+        self.zeros = torch.zeros(4 * n, dtype=torch.int32, device=dev)
+        self.done, self.n_tokens, self.feed = self.zeros[:n], self.zeros[n:2 * n], self.zeros[2 * n:].view(torch.int64)
+        self.pos = torch.zeros(3, n, dtype=pos_dtype, device=dev)
+        self.status = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.state = PagedState(pool)
+        self.state.mode = "decode"
+        self.state.cache_seqlens = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.state.block_table = torch.full((n, width), -1, dtype=torch.int32, device=dev)
+        self.graph = self.logits = None
+
+
+class DecodeGraphs:
+    """The captured decode-step graphs of one model on one pool, kept between packed_generate(graph=...) calls: one graph per batch size,
+    every block table `max_pages_per_prompt` wide (unused entries -1), all captured and replayed on one stream of its own.  `captures`
+    counts the graphs captured so far and `capture_ms` the time spent on them (warm-up forward + capture), so a caller can see reuse."""
+
+    def __init__(self, model, pool: PagedKVPool, max_pages_per_prompt: int):
+        if isinstance(max_pages_per_prompt, bool) or not isinstance(max_pages_per_prompt, int) or max_pages_per_prompt < 1:
+            raise ValueError(f"max_pages_per_prompt must be an int >= 1, got {max_pages_per_prompt!r}")
+        self.model, self.pool, self.max_pages_per_prompt = model, pool, max_pages_per_prompt
+        self.captures, self.capture_ms = 0, 0.0
+        self.stream = None
+        self._steps, self._rings = {}, {}
+
+    def _step(self, n: int, pos_dtype, dev) -> _StepGraph:
+        key = (n, pos_dtype)
+        if key not in self._steps:
+            self._steps[key] = _StepGraph(n, self.max_pages_per_prompt, pos_dtype, self.pool, dev)
+        return self._steps[key]
+
+    def _ring(self, slots: int):
+        if slots not in self._rings:
+            self._rings[slots] = (torch.zeros(slots, 4, dtype=torch.int32).pin_memory(), [torch.cuda.Event() for _ in range(slots)])
+        return self._rings[slots]
+
+
+def _capture(graphs: DecodeGraphs, sg: _StepGraph, model, lm) -> None:
+    """Warm up and capture the decode step over sg's static buffers on the current stream (graphs.stream).  Capture executes nothing and
+    the warm-up is a real forward that writes K / V at cache_seqlens, so the caller runs this where the first decode step belongs and
+    then replays the graph: an exact repeat of the warm-up on unchanged state, which leaves the logits in the static output."""
+    embed = model.get_input_embeddings()
+
+    def step():
+        hidden = lm(inputs_embeds=embed(sg.feed)[None], position_ids=sg.pos[:, None, :], use_cache=False,
+                    vsel_paged=sg.state).last_hidden_state[0]
+        return model.lm_head(hidden)
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    step()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=graphs.stream):          # one stream, no side streams: the graph has no parallel branches
+        sg.logits = step()
+    torch.cuda.synchronize()
+    sg.graph = g
+    graphs.captures += 1
+    graphs.capture_ms += (time.perf_counter() - t0) * 1e3
+
+
+def _graph_decode(model, lm, graphs: DecodeGraphs, logits, step_pos, seqlens, bt, max_new_tokens: int, lookahead: int, eos, select,
+                  return_logits: bool):
+    """The device-resident decode loop.  logits [n, V]: the prefill's; step_pos [3, n], seqlens int32 [n], bt int32 [n, width]: the
+    state of the first decode step; select(logits, step, prev) -> int64 [n] tokens (-1: invalid row).  Per step the host enqueues the
+    selector, ops.decode_advance, a copy of its status into a pinned ring slot with an event, and the graph replay; before step s it
+    reads the status of step s - lookahead.  Rows never leave the batch: decode_advance freezes a finished row, and later replays rewrite
+    one cache slot of that row's own pages with the same values.  -> (tokens, per-step logits or None)"""
+    dev, n = logits.device, logits.shape[0]
+    cur = torch.cuda.current_stream(dev)
+    if graphs.stream is None:
+        graphs.stream = torch.cuda.Stream(dev)
+    s = graphs.stream
+    s.wait_stream(cur)
+    slots = lookahead + 1
+    ring, events = graphs._ring(slots)
+    kept_logits = []
+
+    def status_of(step: int) -> int:
+        events[step % slots].synchronize()
+        active, row, at, _ = ring[step % slots].tolist()
+        if row >= 0:
+            raise RuntimeError(f"sampling failed for prompt {row} at step {at}: {_INVALID_LOGITS}")
+        return active
+
+    try:
+        with torch.cuda.stream(s):
+            sg = graphs._step(n, step_pos.dtype, dev)
+            sg.zeros.zero_()
+            sg.pos.copy_(step_pos)
+            sg.state.cache_seqlens.copy_(seqlens)
+            sg.state.block_table.fill_(-1)
+            sg.state.block_table[:, :bt.shape[1]].copy_(bt)
+            eos_d = _h2d(sorted(eos), torch.int64, dev) if eos else None
+            tokens_out = torch.zeros(n, max_new_tokens, dtype=torch.int64, device=dev)
+            enqueued = checked = 0
+            for step in range(max_new_tokens):
+                if step >= lookahead:
+                    checked = step - lookahead + 1
+                    if status_of(step - lookahead) == 0:
+                        break
+                # every row starts at step 0 together, so the loop index is the step of every active row
+                nxt = select(logits, step, sg.feed if step else None)
+                if return_logits:
+                    kept_logits.append(logits if step == 0 else logits.clone())
+                ops.decode_advance(nxt, eos_d, max_new_tokens, sg.done, sg.n_tokens, sg.state.cache_seqlens, sg.pos, sg.feed, tokens_out,
+                                   sg.status)
+                ring[step % slots].copy_(sg.status, non_blocking=True)
+                events[step % slots].record(s)
+                enqueued = step + 1
+                if step + 1 < max_new_tokens:      # (after the last step every row has stopped: nothing is replayed)
+                    if sg.graph is None:
+                        _capture(graphs, sg, model, lm)
+                    sg.graph.replay()
+                    logits = sg.logits
+            for step in range(checked, enqueued):   # the steps not looked at yet: an invalid row among them still raises
+                status_of(step)
+            counts = sg.n_tokens.tolist()
+            rows = tokens_out.tolist()
+    finally:
+        s.synchronize()                             # also on an exception: nothing in flight writes pages that go back to the free list
+        cur.wait_stream(s)
+    tokens = [rows[b][:counts[b]] for b in range(n)]
+    step_logits = [[kept_logits[i][b] for i in range(counts[b])] for b in range(n)] if return_logits else None
+    return tokens, step_logits
+
+
 @torch.no_grad()
 def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torch.Tensor, image_grid_thw: torch.Tensor,
                     images_per_prompt: Sequence[int], max_new_tokens: int, budgets: float | None = None, eos_token_id=None,
                     page_size: int = 64, pool: PagedKVPool | None = None, return_logits: bool = False, do_sample: bool = False,
-                    temperature: float = 1.0, top_p: float = 1.0, top_k: int = 0, seed: int = 0, repetition_penalty: float = 1.0):
+                    temperature: float = 1.0, top_p: float = 1.0, top_k: int = 0, seed: int = 0, repetition_penalty: float = 1.0,
+                    graph=False, lookahead: int = DEFAULT_LOOKAHEAD):
     """Greedy or sampled generation for a batch of image prompts (arguments as packed_prefill).
     -> dict(tokens: B lists of new token ids (each ends at eos or after max_new_tokens), kept [B], first_logits [B, vocab]
             (bit-identical to packed_prefill's logits), pool, and with return_logits: logits, B lists of [vocab] per step).
@@ -123,9 +262,21 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
     do_sample=False: the next token is the argmax of the logits.  do_sample=True: ops.sample_tokens with temperature, top_k (0: off),
     top_p and seed, as HF's do_sample with those warpers; the draw of prompt b at its s-th new token uses row id b and
     step s, so it does not depend on the other prompts or on when they leave the batch.  A prompt whose logits hold a NaN / +inf
-    (or no finite value) raises RuntimeError."""
+    (or no finite value) raises RuntimeError.
+    graph=False: every decode step is an eager forward and the host reads the step's tokens.  graph=True, or a DecodeGraphs (which keeps
+    the captured graph between calls and fixes the pool): the same tokens and logits from the device-resident loop of DESIGN.md §15 --
+    every prompt holds all its pages from the start, finished prompts stay in the batch as frozen rows, and the host reads a status
+    word `lookahead` (>= 1) steps behind the step it enqueues."""
     if max_new_tokens < 1:
         raise ValueError("max_new_tokens must be >= 1")
+    if not isinstance(graph, (bool, DecodeGraphs)):
+        raise TypeError(f"graph must be a bool or a DecodeGraphs, got {graph!r}")
+    if isinstance(lookahead, bool) or not isinstance(lookahead, int) or lookahead < 1:
+        raise ValueError(f"lookahead must be an int >= 1, got {lookahead!r}")
+    if isinstance(graph, DecodeGraphs):
+        if graph.model is not model or (pool is not None and pool is not graph.pool):
+            raise ValueError("this DecodeGraphs was built for another model / pool")
+        pool = graph.pool
     if not isinstance(do_sample, bool):
         raise TypeError(f"do_sample must be a bool, got {do_sample!r}")
     if do_sample:
@@ -148,12 +299,23 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
     elif pool.page_size != page_size or pool.hkv != hkv or pool.head_dim != hd or len(pool.k) != len(lm.layers):
         raise ValueError("the pool's geometry does not match the model / page_size")
     width = max(most)
+    graphs = graph if isinstance(graph, DecodeGraphs) else (DecodeGraphs(model, pool, width) if graph else None)
+    if graphs is not None and width > graphs.max_pages_per_prompt:
+        raise ValueError(f"a prompt needs {width} pages, this DecodeGraphs holds {graphs.max_pages_per_prompt} per prompt")
     pages = [[] for _ in range(n)]
     state = PagedState(pool)
     old_impl = lm.config._attn_implementation
     try:
-        for b, L in enumerate(lengths):
-            pages[b] = pool.alloc(_cdiv(L, page_size))
+        if graphs is not None:
+            # all pages up front: the block table is constant for the call.  most[b] pages hold the L + max_new_tokens - 1 keys of a
+            # prompt that runs to the limit; a row frozen on eos at token s <= max_new_tokens - 2 keeps cache_seqlens = L + s inside them
+            drawn = pool.alloc(sum(most))
+            for b, m in enumerate(most):
+                pages[b], drawn = drawn[:m], drawn[m:]
+                assert len(pages[b]) * page_size >= lengths[b] + max_new_tokens - 1
+        else:
+            for b, L in enumerate(lengths):
+                pages[b] = pool.alloc(_cdiv(L, page_size))
         bt = _h2d([pg + [-1] * (width - len(pg)) for pg in pages], torch.int32, dev)
         # prefill: the packed prompts through the LLM; each layer also appends its keys / values, token t into row
         # prompt(t) of the block table at its position
@@ -180,7 +342,19 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
         prev = None                                                   # the last step's tokens, which join the sets at this step
         state.mode = "decode"
         step = 0
-        while True:
+        if graphs is not None:
+            def select(lg, at, prv):                                  # the eager loop's selector launches, rows = prompts throughout
+                if penalize and do_sample:
+                    pen = ops.repetition_penalty(lg, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prv)
+                    return ops.sample_tokens(pen, temperature, top_p, top_k, seed, row_ids=row_ids, step=at)
+                if penalize:
+                    return ops.repetition_penalty(lg, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prv, return_tokens=True)
+                if do_sample:
+                    return ops.sample_tokens(lg, temperature, top_p, top_k, seed, row_ids=row_ids, step=at)
+                return lg.argmax(-1)
+            tokens, step_logits = _graph_decode(model, lm, graphs, logits, step_pos, seqlens, bt, max_new_tokens, lookahead, eos, select,
+                                                return_logits)
+        while graphs is None:
             if penalize and do_sample:
                 pen = ops.repetition_penalty(logits, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prev)
                 nxt = ops.sample_tokens(pen, temperature, top_p, top_k, seed, row_ids=row_ids, step=step)
@@ -194,7 +368,7 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
             keep = []
             for i, b in enumerate(active):
                 if host[i] < 0:
-                    raise RuntimeError(f"sampling failed for prompt {b} at step {step}: its logits hold a NaN / +inf or no finite value")
+                    raise RuntimeError(f"sampling failed for prompt {b} at step {step}: {_INVALID_LOGITS}")
                 tokens[b].append(host[i])
                 if return_logits:
                     step_logits[b].append(logits[i])

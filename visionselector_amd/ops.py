@@ -1042,10 +1042,38 @@ def repetition_penalty(logits: torch.Tensor, penalty: float, sets: torch.Tensor,
     return tokens if out is None else (out, tokens)
 
 
+def decode_advance(next_tokens: torch.Tensor, eos: Optional[torch.Tensor], max_new_tokens: int, done: torch.Tensor, n_tokens: torch.Tensor,
+                   cache_seqlens: torch.Tensor, pos: torch.Tensor, feed: torch.Tensor, tokens_out: torch.Tensor, status: torch.Tensor) -> None:
+    """vsel_decode_advance: the bookkeeping of one decode step, on the device.  next_tokens int64 [B] from the step's
+    selector; eos int64 [n_eos] on the device or None; state updated in place: done int32 [B] (0 active, 1 eos, 2 length, 3 invalid
+    logits), n_tokens int32 [B], cache_seqlens int32 [B], pos int32 / int64 [3, B], feed int64 [B], tokens_out int64 [B, max_new_tokens],
+    status int32 [4] = {rows still active, lowest row that turned invalid in this launch or -1, its n_tokens or -1, 0}.  All contiguous.
+    One launch, no allocation, no host synchronisation: capturable.  Shapes and dtypes are checked before any device work."""
+    if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
+        raise ValueError(f"max_new_tokens must be an int >= 1, got {max_new_tokens!r}")
+    if next_tokens.dtype != torch.int64 or next_tokens.dim() != 1:
+        raise TypeError("next_tokens must be int64 [B]")
+    b = next_tokens.shape[0]
+    for name, t, dt, shape in (("done", done, torch.int32, (b,)), ("n_tokens", n_tokens, torch.int32, (b,)),
+                               ("cache_seqlens", cache_seqlens, torch.int32, (b,)), ("feed", feed, torch.int64, (b,)),
+                               ("tokens_out", tokens_out, torch.int64, (b, max_new_tokens)), ("status", status, torch.int32, (4,))):
+        if t.dtype != dt or tuple(t.shape) != shape:
+            raise TypeError(f"{name} must be {dt} {list(shape)}, got {t.dtype} {list(t.shape)}")
+    if pos.dtype not in (torch.int32, torch.int64) or tuple(pos.shape) != (3, b):
+        raise TypeError(f"pos must be int32 / int64 [3, {b}], got {pos.dtype} {list(pos.shape)}")
+    if eos is not None and (eos.dtype != torch.int64 or eos.dim() != 1):
+        raise TypeError("eos must be int64 [n_eos] or None")
+    _dev(next_tokens, eos, done, n_tokens, cache_seqlens, pos, feed, tokens_out, status)
+    n_eos = 0 if eos is None else eos.shape[0]
+    N.check(N.lib().vsel_decode_advance(_stream(), next_tokens.data_ptr(), b, _p(eos) if n_eos else None, n_eos, max_new_tokens,
+                                        done.data_ptr(), n_tokens.data_ptr(), cache_seqlens.data_ptr(), pos.data_ptr(),
+                                        int(pos.dtype == torch.int64), feed.data_ptr(), tokens_out.data_ptr(), status.data_ptr()))
+
+
 # every op that reaches libvsel switches to its tensors' device first
 for _name in ("lis_scores", "lis_select", "lis_select_permuted", "gelu_colsum", "colsum_linear", "lis_select_presummed", "lis_select_varlen",
               "hard_topk", "gather_rows", "soft_topk_fwd", "soft_topk_bwd", "lis_train_fwd", "lis_train_bwd", "lis_train_bwd_factors", "factors_to_grads", "lis_scores_bwd",
               "splice", "splice_batched", "lis_select_splice", "topk_select_splice", "varlen_attn", "varlen_attn_fwd_lse", "varlen_attn_bwd", "varlen_attn_kv",
-              "attn_head_major", "paged_attn", "kvcache_attn", "sample_tokens", "token_sets", "repetition_penalty"):
+              "attn_head_major", "paged_attn", "kvcache_attn", "sample_tokens", "token_sets", "repetition_penalty", "decode_advance"):
     globals()[_name] = _device_guard(globals()[_name])
 del _name
