@@ -306,7 +306,8 @@ int vsel_topk_select_splice(void* stream, const void* h, vsel_dtype hdtype, int6
  * of EV/qwen25vl/modeling_qwen2_5_vl.py:900 / OV/llavaonevision1_5/modeling_llavaonevision1_5.py:686.
  *   q [T, Hq, d], k/v [T, Hkv, d] bf16, already rotated; cu_seqlens DEVICE int32 [n_seq + 1]
  *   (the tensor the reference passes as `attention_mask`); out [T, Hq, d] bf16.  d in {128 (the LLMs), 80, 64 (vision towers)}.
- * Math: softmax(q k^T * scale + causal) v with fp32 softmax (EV/qwen25vl/modeling_qwen2_5_vl.py:777-797). */
+ * Math: softmax(q k^T * scale + causal) v with fp32 softmax (EV/qwen25vl/modeling_qwen2_5_vl.py:777-797).
+ * scale must be finite and > 0 (VSEL_ERR_INVALID otherwise, checked before any HIP call). */
 int vsel_varlen_attn_fwd(void* stream, const void* q, const void* k, const void* v, const int32_t* cu_seqlens,
                          int64_t n_seq, int64_t max_seqlen, int64_t total, int64_t hq, int64_t hkv, int64_t d,
                          float scale, int causal, void* out);
@@ -316,7 +317,8 @@ int vsel_varlen_attn_fwd(void* stream, const void* q, const void* k, const void*
  * k_cache / v_cache [n_pages, page_size, Hkv, d] bf16.  Causal masking is bottom-right aligned (query i of a sequence sees
  * keys <= i + (seqlens_k - q_len)), i.e. chunked prefill / prefill-with-prefix / decode against the compressed cache.
  * No reference counterpart beyond the flash-attn call sites above (the reference keeps a contiguous HF DynamicCache);
- * the north-star asks for a "paged / var-len" kernel.  Rows that see no key output zeros.                               */
+ * the north-star asks for a "paged / var-len" kernel.  Rows that see no key output zeros.
+ * scale must be finite and > 0 (VSEL_ERR_INVALID otherwise, checked before any HIP call). */
 int vsel_paged_attn_fwd(void* stream, const void* q, const void* k_cache, const void* v_cache,
                         const int32_t* cu_seqlens_q, const int32_t* seqlens_k, const int32_t* block_table,
                         int64_t max_pages_per_seq, int64_t page_size, int64_t n_seq, int64_t max_seqlen_q, int64_t hq,
@@ -324,7 +326,8 @@ int vsel_paged_attn_fwd(void* stream, const void* q, const void* k_cache, const 
 
 /* Same kernel with separate query / key packings (flash_attn_varlen_func's general form: cu_seqlens_q != cu_seqlens_k):
  * sequence s owns query rows [cu_seqlens_q[s], cu_seqlens_q[s+1]) of q and key rows [cu_seqlens_k[s], +seqlens_k[s]) of
- * k / v (contiguous, [total_k, hkv, d]); causal masking is bottom-right aligned (flash-attn >= 2.1).  Forward only.     */
+ * k / v (contiguous, [total_k, hkv, d]); causal masking is bottom-right aligned (flash-attn >= 2.1).  Forward only.
+ * scale must be finite and > 0 (VSEL_ERR_INVALID otherwise, checked before any HIP call). */
 int vsel_varlen_attn_fwd_kv(void* stream, const void* q, const void* k, const void* v, const int32_t* cu_seqlens_q,
                             const int32_t* cu_seqlens_k, const int32_t* seqlens_k, int64_t n_seq, int64_t max_seqlen_q,
                             int64_t hq, int64_t hkv, int64_t d, float scale, int causal, void* out);
@@ -334,7 +337,8 @@ int vsel_varlen_attn_fwd_kv(void* stream, const void* q, const void* k, const vo
  * row l, head h) of q lives at  cu_seqlens_q[s] * hq * d + l * q_row_stride + h * q_head_stride  (k and v likewise with
  * cu_seqlens_k or cu_seqlens_q, hkv and their own strides -- HF keeps v as a transposed view of the packed projection); packed [T, H, d] is row stride H * d, head stride d, head-major
  * is row stride d, head stride L * d with cu = [0, L, 2L, ...].  cu_seqlens_k / seqlens_k NULL: keys share the query
- * packing.  out is always packed [T, hq, d].  Saves the two transposing copies per layer of the HF path.             */
+ * packing.  out is always packed [T, hq, d].  Saves the two transposing copies per layer of the HF path.
+ * scale must be finite and > 0 (VSEL_ERR_INVALID otherwise, checked before any HIP call). */
 int vsel_varlen_attn_fwd_strided(void* stream, const void* q, const void* k, const void* v, const int32_t* cu_seqlens_q,
                                  const int32_t* cu_seqlens_k, const int32_t* seqlens_k, int64_t n_seq, int64_t max_seqlen_q,
                                  int64_t hq, int64_t hkv, int64_t d, int64_t q_row_stride, int64_t q_head_stride,
@@ -367,7 +371,8 @@ int vsel_varlen_attn_fwd_strided(void* stream, const void* q, const void* k, con
  * Device values are never read on the host: a row whose end + seqlen_new exceeds its capacity (or whose cache_batch_idx is out of
  * [0, B_cache)) is written only inside its capacity and attends to at most that many keys -- a caller error with an unspecified
  * result for that row, never an access outside k_cache / v_cache / the tables.  Workspace (256-byte aligned):
- * vsel_kvcache_attn_workspace_bytes(batch, seqlen_q, hq, d) -- per-row metadata and the q copy.                              */
+ * vsel_kvcache_attn_workspace_bytes(batch, seqlen_q, hq, d) -- per-row metadata and the q copy.
+ * scale must be finite and > 0 (VSEL_ERR_INVALID otherwise, checked before any HIP call), also for an append-only call. */
 size_t vsel_kvcache_attn_workspace_bytes(int64_t batch, int64_t seqlen_q, int64_t hq, int64_t d);
 int vsel_kvcache_attn_fwd(void* stream, const void* q, int64_t q_batch_stride, int64_t q_row_stride, int64_t q_head_stride,
                           void* k_cache, void* v_cache, int64_t cache_rows, int64_t cache_len, const int32_t* block_table,
@@ -435,7 +440,8 @@ int vsel_decode_advance(void* stream, const int64_t* next, int64_t batch, const 
  * launch (csrc/attn_fwd64_parts.hip; the reference's call is the same flash_attn_varlen_func, EV/qwen25vl/modeling_qwen2_5_vl.py:900).
  * vsel_varlen_attn_fwd_workspace_bytes: bytes the call would use for these shapes, 0 when it would run the workspace-free forms
  * (then ws may be NULL; the call is vsel_varlen_attn_fwd[_lse]).  Deterministic; not bit-identical to the workspace-free forms
- * (another fp32 association: within a bf16 rounding).  head_dim 128, causal, every sequence max_seqlen tokens.                    */
+ * (another fp32 association: within a bf16 rounding).  head_dim 128, causal, every sequence max_seqlen tokens.
+ * scale must be finite and > 0 (VSEL_ERR_INVALID otherwise, checked before any HIP call). */
 size_t vsel_varlen_attn_fwd_workspace_bytes(int64_t n_seq, int64_t max_seqlen, int64_t total, int64_t hq, int64_t hkv, int64_t d, int causal);
 int vsel_varlen_attn_fwd_ws(void* stream, const void* q, const void* k, const void* v, const int32_t* cu_seqlens, int64_t n_seq,
                             int64_t max_seqlen, int64_t total, int64_t hq, int64_t hkv, int64_t d, float scale, int causal, void* out,
@@ -449,7 +455,9 @@ int vsel_varlen_attn_fwd_ws(void* stream, const void* q, const void* k, const vo
  *     visible keys (natural log).
  *   vsel_varlen_attn_bwd: dout, out [total, hq, 128] bf16, lse from the forward -> dq [total, hq, 128], dk, dv
  *     [total, hkv, 128] bf16 (overwritten; GQA groups are summed in fp32 inside the kernel).  q and k share cu_seqlens.
- *     Deterministic: no float atomics, reruns are bit-identical.  Workspace: vsel_varlen_attn_bwd_workspace_bytes.     */
+ *     Deterministic: no float atomics, reruns are bit-identical.  Workspace: vsel_varlen_attn_bwd_workspace_bytes.
+ *   Both: scale must be finite and > 0 (VSEL_ERR_INVALID otherwise, checked before any HIP call).  The backward takes the scale of the forward
+ *   that produced out / lse. */
 int vsel_varlen_attn_fwd_lse(void* stream, const void* q, const void* k, const void* v, const int32_t* cu_seqlens,
                              int64_t n_seq, int64_t max_seqlen, int64_t total, int64_t hq, int64_t hkv, int64_t d,
                              float scale, int causal, void* out, float* lse);

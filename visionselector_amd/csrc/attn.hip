@@ -808,20 +808,20 @@ int attn::attn_launch_cache(hipStream_t st, const void* q, const void* k, const 
 }
 
 static int attn_checks(const void* q, const void* k, const void* v, const int32_t* cu, const void* out, int64_t n_seq,
-                       int64_t max_seqlen, int64_t hq, int64_t hkv, int64_t d) {
+                       int64_t max_seqlen, int64_t hq, int64_t hkv, int64_t d, float scale) {
   if (!q || !k || !v || !cu || !out) return fail(VSEL_ERR_INVALID, "NULL pointer");
   if (d != 128 && d != 80 && d != 64) return fail(VSEL_ERR_UNSUPPORTED, "head_dim %lld not in {64, 80, 128}", (long long)d);
   if (n_seq < 1 || max_seqlen < 1 || hq < 1 || hkv < 1 || hq % hkv != 0 || n_seq > (1 << 24) || hq > 65535)
     return fail(VSEL_ERR_INVALID, "bad attention shape (n_seq=%lld max_seqlen=%lld hq=%lld hkv=%lld)", (long long)n_seq,
                 (long long)max_seqlen, (long long)hq, (long long)hkv);
   if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) return fail(VSEL_ERR_INVALID, "q/k/v/out must be 16-byte aligned");
-  return VSEL_OK;
+  return check_softmax_scale(scale);
 }
 
 extern "C" int vsel_varlen_attn_fwd(void* stream, const void* q, const void* k, const void* v, const int32_t* cu_seqlens,
                                     int64_t n_seq, int64_t max_seqlen, int64_t total, int64_t hq, int64_t hkv, int64_t d,
                                     float scale, int causal, void* out) {
-  int rc = attn_checks(q, k, v, cu_seqlens, out, n_seq, max_seqlen, hq, hkv, d);
+  int rc = attn_checks(q, k, v, cu_seqlens, out, n_seq, max_seqlen, hq, hkv, d, scale);
   if (rc) return rc;
   if (total < 1) return fail(VSEL_ERR_INVALID, "total must be >= 1");
   hipStream_t st = (hipStream_t)stream;
@@ -859,7 +859,7 @@ extern "C" size_t vsel_varlen_attn_fwd_workspace_bytes(int64_t n_seq, int64_t ma
 extern "C" int vsel_varlen_attn_fwd_ws(void* stream, const void* q, const void* k, const void* v, const int32_t* cu_seqlens, int64_t n_seq,
                                        int64_t max_seqlen, int64_t total, int64_t hq, int64_t hkv, int64_t d, float scale, int causal,
                                        void* out, float* lse, void* ws, size_t ws_bytes) {
-  int rc = attn_checks(q, k, v, cu_seqlens, out, n_seq, max_seqlen, hq, hkv, d);
+  int rc = attn_checks(q, k, v, cu_seqlens, out, n_seq, max_seqlen, hq, hkv, d, scale);
   if (rc) return rc;
   if (total < 1) return fail(VSEL_ERR_INVALID, "total must be >= 1");
   hipStream_t st = (hipStream_t)stream;
@@ -874,7 +874,7 @@ extern "C" int vsel_varlen_attn_fwd_ws(void* stream, const void* q, const void* 
 extern "C" int vsel_varlen_attn_fwd_lse(void* stream, const void* q, const void* k, const void* v, const int32_t* cu_seqlens,
                                         int64_t n_seq, int64_t max_seqlen, int64_t total, int64_t hq, int64_t hkv, int64_t d,
                                         float scale, int causal, void* out, float* lse) {
-  int rc = attn_checks(q, k, v, cu_seqlens, out, n_seq, max_seqlen, hq, hkv, d);
+  int rc = attn_checks(q, k, v, cu_seqlens, out, n_seq, max_seqlen, hq, hkv, d, scale);
   if (rc) return rc;
   if (total < 1 || !lse) return fail(VSEL_ERR_INVALID, "total must be >= 1 and lse non-NULL");
   hipStream_t st = (hipStream_t)stream;
@@ -887,7 +887,7 @@ extern "C" int vsel_varlen_attn_fwd_kv(void* stream, const void* q, const void* 
                                        const int32_t* cu_seqlens_k, const int32_t* seqlens_k, int64_t n_seq,
                                        int64_t max_seqlen_q, int64_t hq, int64_t hkv, int64_t d, float scale, int causal,
                                        void* out) {
-  int rc = attn_checks(q, k, v, cu_seqlens_q, out, n_seq, max_seqlen_q, hq, hkv, d);
+  int rc = attn_checks(q, k, v, cu_seqlens_q, out, n_seq, max_seqlen_q, hq, hkv, d, scale);
   if (rc) return rc;
   if (!cu_seqlens_k || !seqlens_k) return fail(VSEL_ERR_INVALID, "cu_seqlens_k / seqlens_k is NULL");
   hipStream_t st = (hipStream_t)stream;
@@ -901,7 +901,7 @@ extern "C" int vsel_varlen_attn_fwd_strided(void* stream, const void* q, const v
                                             int64_t max_seqlen_q, int64_t hq, int64_t hkv, int64_t d, int64_t q_row_stride,
                                             int64_t q_head_stride, int64_t k_row_stride, int64_t k_head_stride,
                                             int64_t v_row_stride, int64_t v_head_stride, float scale, int causal, void* out) {
-  int rc = attn_checks(q, k, v, cu_seqlens_q, out, n_seq, max_seqlen_q, hq, hkv, d);
+  int rc = attn_checks(q, k, v, cu_seqlens_q, out, n_seq, max_seqlen_q, hq, hkv, d, scale);
   if (rc) return rc;
   if ((cu_seqlens_k == nullptr) != (seqlens_k == nullptr)) return fail(VSEL_ERR_INVALID, "give cu_seqlens_k and seqlens_k together");
   if (q_row_stride < d || q_head_stride < d || k_row_stride < d || k_head_stride < d || v_row_stride < d || v_head_stride < d ||
@@ -917,7 +917,7 @@ extern "C" int vsel_paged_attn_fwd(void* stream, const void* q, const void* k_ca
                                    const int32_t* cu_seqlens_q, const int32_t* seqlens_k, const int32_t* block_table,
                                    int64_t max_pages_per_seq, int64_t page_size, int64_t n_seq, int64_t max_seqlen_q, int64_t hq,
                                    int64_t hkv, int64_t d, float scale, int causal, void* out) {
-  int rc = attn_checks(q, k_cache, v_cache, cu_seqlens_q, out, n_seq, max_seqlen_q, hq, hkv, d);
+  int rc = attn_checks(q, k_cache, v_cache, cu_seqlens_q, out, n_seq, max_seqlen_q, hq, hkv, d, scale);
   if (rc) return rc;
   if (!seqlens_k || !block_table) return fail(VSEL_ERR_INVALID, "seqlens_k / block_table is NULL");
   if (page_size < 1 || page_size > (1 << 20) || max_pages_per_seq < 1 || max_pages_per_seq > (1ll << 31) - 1)

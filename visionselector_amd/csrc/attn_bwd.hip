@@ -1033,6 +1033,7 @@ extern "C" int vsel_varlen_attn_bwd(void* stream, const void* dout, const void* 
   if (((uintptr_t)dout | (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)dq | (uintptr_t)dk |
        (uintptr_t)dv | (uintptr_t)workspace) & 15)
     return fail(VSEL_ERR_INVALID, "attention tensors must be 16-byte aligned");
+  if (int rc = attn::check_softmax_scale(scale)) return rc;
   // the dK / dV item form is decided ONCE per call (the knobs are read here and nowhere below): the workspace check and the launch cannot
   // disagree when a knob changes on another thread in between.  NOTE: the form depends on the call's total / mean / longest length, and each
   // form associates the fp32 sums of a group's q heads differently -- unlike the forward, a sequence's dK / dV may differ by one bf16

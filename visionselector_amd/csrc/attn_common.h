@@ -88,6 +88,14 @@ struct PagedKV {
   int64_t q_row_stride, q_head_stride, kv_row_stride, kv_head_stride, v_row_stride, v_head_stride;   // v_*: 0 = same as k
 };
 
+// Argument check shared by every C-ABI attention entry that takes `scale`: finite and > 0.  The kernels rely on it -- the running
+// maximum is taken on the scaled scores (max commutes with the scaling only for scale > 0), and a NaN / inf scale poisons every row.
+inline int check_softmax_scale(float scale) {
+  if (!(scale > 0.f && scale <= 3.402823466e38f))
+    return fail(VSEL_ERR_INVALID, "softmax scale %g must be finite and > 0", (double)scale);
+  return VSEL_OK;
+}
+
 // attn.hip's form selection and launch, for the attention half of vsel_kvcache_attn_fwd (kvcache.hip): queries packed per cu_q,
 // keys per pg (seqlens_k always set; page table or contiguous rows at cu_k)
 int attn_launch_cache(hipStream_t st, const void* q, const void* k, const void* v, const int32_t* cu_q, int64_t n_seq, int64_t max_seqlen_q,

@@ -166,6 +166,7 @@ extern "C" int vsel_kvcache_attn_fwd(void* stream, const void* q, int64_t q_batc
   if (batch * seqlen_q >= (1ll << 31)) return fail(VSEL_ERR_UNSUPPORTED, "more than 2^31 - 1 query rows");
   if (seqlen_new > 0 && (!k || !v)) return fail(VSEL_ERR_INVALID, "seqlen_new > 0 needs k and v");
   if (cache_rows < 1 || cache_len < 1) return fail(VSEL_ERR_INVALID, "empty cache");
+  if (int rc = attn::check_softmax_scale(scale)) return rc;
   if (block_table) {
     if (cache_batch_idx || cache_leftpad) return fail(VSEL_ERR_UNSUPPORTED, "a paged cache takes neither cache_batch_idx nor cache_leftpad");
     if (max_pages < 1 || max_pages > (1 << 24) || cache_len > (1 << 20)) return fail(VSEL_ERR_INVALID, "bad page geometry");
