@@ -1,4 +1,4 @@
-"""packed_generate with repetition_penalty on the tiny selector model of tests/test_generate_gpu.py (imported from that module): greedy tokens
+"""packed_generate with repetition_penalty on the tiny selector model of tests/generate_model.py: greedy tokens
 against the batch-1 HF generate() with the same penalty (the tie rule of test_generate_gpu.py on HF's processed scores), the token sets
 built from the prompts as passed (image ids the selector dropped included), sampled tokens as ops.sample_tokens of HF's processed
 logits, 1.0 as the path without the penalty, hf_generation_kwargs driving packed_generate from the model's generation_config, and every
@@ -6,14 +6,20 @@ page back on the pool."""
 import pytest
 import torch
 
-from test_generate_gpu import IMG, VEND, VSTART, _compare, _sub, setup  # noqa: F401  (module fixture: the tiny model and its prompts)
+import generate_model
+from generate_model import IMG, VEND, VSTART, _compare, _sub
 
 pytestmark = pytest.mark.gpu
 
 SAMPLE = dict(temperature=0.8, top_p=0.9, top_k=20, seed=1234)
 
 
-def _hf_batch1(model, setup, b, **kw):  # noqa: F811
+@pytest.fixture(scope="module")
+def setup():
+    return generate_model.build()
+
+
+def _hf_batch1(model, setup, b, **kw):
     one, p1, g1, _ = _sub(setup, [b])
     inp = dict(input_ids=one[0][None].cuda(), attention_mask=torch.ones_like(one[0])[None].cuda(), pixel_values=p1,
                image_grid_thw=g1, mm_token_type_ids=(one[0] == IMG).int()[None].cuda())
@@ -28,7 +34,7 @@ def _processed(ids, logits, theta):
     return RepetitionPenaltyLogitsProcessor(penalty=float(theta))(torch.as_tensor(ids, device="cuda")[None], logits.float()[None])[0]
 
 
-def test_greedy_matches_batch1_generate_with_penalty(setup):  # noqa: F811
+def test_greedy_matches_batch1_generate_with_penalty(setup):
     from visionselector_amd.generate import PagedKVPool, packed_generate
     model = setup[0]
     ids, pix, grids, ipp = _sub(setup, [0, 1, 2])
@@ -51,7 +57,7 @@ def test_greedy_matches_batch1_generate_with_penalty(setup):  # noqa: F811
     assert compared >= 3
 
 
-def test_sets_hold_the_prompts_as_passed(setup, monkeypatch):  # noqa: F811
+def test_sets_hold_the_prompts_as_passed(setup, monkeypatch):
     """The sets come from the uncompressed ids: every image-pad id (also of the visual tokens the selector dropped) and the
     vision start / end ids are in, as in HF generate(), which keeps the full input_ids while the selector compresses inside forward."""
     from visionselector_amd import ops
@@ -79,7 +85,7 @@ def test_sets_hold_the_prompts_as_passed(setup, monkeypatch):  # noqa: F811
         assert bits == set(ids[b].tolist()) and {IMG, VSTART, VEND} <= bits
 
 
-def test_sampled_tokens_are_sample_tokens_of_processed_logits(setup):  # noqa: F811
+def test_sampled_tokens_are_sample_tokens_of_processed_logits(setup):
     from visionselector_amd import ops
     from visionselector_amd.generate import packed_generate
     model = setup[0]
@@ -101,7 +107,7 @@ def test_sampled_tokens_are_sample_tokens_of_processed_logits(setup):  # noqa: F
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(do_sample=True, **SAMPLE)])
-def test_penalty_one_is_the_path_without_it(setup, kw):  # noqa: F811
+def test_penalty_one_is_the_path_without_it(setup, kw):
     from visionselector_amd.generate import packed_generate
     model = setup[0]
     ids, pix, grids, ipp = _sub(setup, [0, 1, 2])
@@ -113,7 +119,7 @@ def test_penalty_one_is_the_path_without_it(setup, kw):  # noqa: F811
         assert all(torch.equal(x, y) for x, y in zip(same["logits"][b], base["logits"][b]))
 
 
-def test_hf_generation_kwargs_drives_packed_generate(setup):  # noqa: F811
+def test_hf_generation_kwargs_drives_packed_generate(setup):
     from visionselector_amd.generate import PagedKVPool, hf_generation_kwargs, packed_generate
     model = setup[0]
     ids, pix, grids, ipp = _sub(setup, [0, 1, 2])
@@ -135,7 +141,7 @@ def test_hf_generation_kwargs_drives_packed_generate(setup):  # noqa: F811
         model.generation_config.repetition_penalty = old
 
 
-def test_invalid_penalty_refused_before_device_work(setup):  # noqa: F811
+def test_invalid_penalty_refused_before_device_work(setup):
     from visionselector_amd.generate import packed_generate
     model = setup[0]
     ids, pix, grids, ipp = _sub(setup, [0])

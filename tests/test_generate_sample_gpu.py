@@ -1,17 +1,23 @@
-"""packed_generate with do_sample on the tiny selector model of tests/test_generate_gpu.py (imported from that module): greedy stays
+"""packed_generate with do_sample on the tiny selector model of tests/generate_model.py: greedy stays
 the default code path, sampled runs are repeatable, each token is ops.sample_tokens of its own step's logits at row id = prompt and
 step = tokens generated before it (also after prompts have left the batch), top_k = 1 is greedy, pages return to the pool."""
 import pytest
 import torch
 
-from test_generate_gpu import _sub, setup  # noqa: F401  (module fixture: the tiny model and its prompts)
+import generate_model
+from generate_model import _sub
 
 pytestmark = pytest.mark.gpu
 
 SAMPLE = dict(temperature=0.8, top_p=0.9, top_k=20, seed=1234)
 
 
-def test_do_sample_false_is_the_default_path(setup):  # noqa: F811
+@pytest.fixture(scope="module")
+def setup():
+    return generate_model.build()
+
+
+def test_do_sample_false_is_the_default_path(setup):
     from visionselector_amd.generate import packed_generate
     model = setup[0]
     ids, pix, grids, ipp = _sub(setup, [0, 1, 2])
@@ -21,7 +27,7 @@ def test_do_sample_false_is_the_default_path(setup):  # noqa: F811
     assert torch.equal(same["first_logits"], base["first_logits"])
 
 
-def test_sampling_is_repeatable_and_seeded(setup):  # noqa: F811
+def test_sampling_is_repeatable_and_seeded(setup):
     from visionselector_amd.generate import packed_generate
     model = setup[0]
     ids, pix, grids, ipp = _sub(setup, [0, 1, 2])
@@ -32,7 +38,7 @@ def test_sampling_is_repeatable_and_seeded(setup):  # noqa: F811
     assert a["tokens"] != c["tokens"]
 
 
-def test_each_token_is_sample_tokens_of_its_step(setup):  # noqa: F811
+def test_each_token_is_sample_tokens_of_its_step(setup):
     """row id = the prompt's index, step = tokens generated so far -- also once a prompt has left the batch at eos"""
     from visionselector_amd import ops
     from visionselector_amd.generate import PagedKVPool, packed_generate
@@ -57,7 +63,7 @@ def test_each_token_is_sample_tokens_of_its_step(setup):  # noqa: F811
     assert checked > 8
 
 
-def test_top_k_1_is_greedy(setup):  # noqa: F811
+def test_top_k_1_is_greedy(setup):
     from visionselector_amd.generate import packed_generate
     model = setup[0]
     ids, pix, grids, ipp = _sub(setup, [0, 1, 2])
@@ -74,7 +80,7 @@ def test_top_k_1_is_greedy(setup):  # noqa: F811
     assert compared >= 12
 
 
-def test_invalid_parameters_refused_before_device_work(setup):  # noqa: F811
+def test_invalid_parameters_refused_before_device_work(setup):
     from visionselector_amd.generate import packed_generate
     model = setup[0]
     ids, pix, grids, ipp = _sub(setup, [0])

@@ -7,7 +7,7 @@ Kernel level: V = 152 064 (Qwen2.5-VL), B in {1, 8, 32, 64}, bf16 and fp32 logit
 generated ids.  The greedy mode (penalty + argmax -> tokens) and the fp32-out mode (y for the sampler) against HF's chain on the same
 logits (float(), RepetitionPenaltyLogitsProcessor on the [B, L + s] id matrix, argmax).  Wall time per call from device events around 50
 back-to-back calls; the library's device time from its per-kernel profile (vsel_profile_*: host gaps excluded).
-Model level: tools/bench_sample.py's 7B-geometry selector model (random bf16 weights, B prompts of 2304 visual + 64 text tokens,
+Model level: tools/generate_common.py's 7B-geometry selector model (random bf16 weights, B prompts of 2304 visual + 64 text tokens,
 budget 0.2, N new tokens); packed_generate with repetition_penalty 1.05 against 1.0, greedy and sampled (T 0.7, top_p 0.9, top_k 50),
 no eos so that every run produces B x N tokens; runs alternate, best of two each."""
 import argparse
@@ -19,7 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bench_sample import _stamp, _time_us, build_model  # noqa: E402
+from generate_common import _stamp, _time_us, model_and_prompts  # noqa: E402
 from visionselector_amd import _native as N  # noqa: E402
 from visionselector_amd import ops  # noqa: E402
 
@@ -66,13 +66,7 @@ def kernel_level():
 
 def model_level(batches, new_tokens):
     from visionselector_amd.generate import packed_generate
-    model, prompts, pix, (IMG, VSTART, VEND, n_vis, n_text, g) = build_model()
-    for _ in range(max(batches)):
-        pre = torch.randint(1000, 5000, (n_text // 2,), generator=g)
-        post = torch.randint(1000, 5000, (n_text - n_text // 2 - 2,), generator=g)
-        prompts.append(torch.cat((pre, torch.tensor([VSTART]), torch.full((n_vis,), IMG), torch.tensor([VEND]), post)))
-        pix.append(torch.randn(96 * 96, 3 * 2 * 14 * 14, generator=g).bfloat16())
-    grid_t = torch.tensor([[1, 96, 96]]).cuda()
+    model, prompts, pix, grid_t, n_vis, n_text = model_and_prompts(max(batches))
     sample = dict(do_sample=True, temperature=0.7, top_p=0.9, top_k=50, seed=1)
     modes = {"greedy": dict(), "greedy_rp1.05": dict(repetition_penalty=THETA), "sample": sample,
              "sample_rp1.05": dict(sample, repetition_penalty=THETA)}

@@ -2,20 +2,20 @@
 
 packed_prefill stops at the first token.  packed_generate continues from the same packed inputs (packed._packed_inputs: tower,
 M-RoPE positions, ragged LIS, splice) and decodes every prompt of the batch together:
-  prefill  the LLM over the packed compressed prompts with the var-len attention over cu_seqlens' (the calls packed_prefill
+  prefill  (_prefill) the LLM over the packed compressed prompts with the var-len attention over cu_seqlens' (the calls packed_prefill
            makes), plus ONE append launch per layer that writes the prompts' keys / values into their pages;
-  decode   one new token per active prompt, packed as [1, B_active, D]: per layer one vsel_kvcache_attn_fwd (append launch +
-           attention over the prompt's pages).
+  decode   (_eager_decode) one new token per active prompt, packed as [1, B_active, D]: per layer one vsel_kvcache_attn_fwd
+           (append launch + attention over the prompt's pages).
 The attention interface `vsel_paged` (register_paged_attention) reads the layer's pools through `module.layer_idx` and the
 paged state from the `vsel_paged` keyword argument of the LLM forward -- the route packed_prefill uses for cu_seq_lens_q.
 Page allocation is host bookkeeping: lengths are known from the kept-token counts and the step count, so nothing reads device
 memory except the next tokens -- the greedy argmax, or with do_sample ops.sample_tokens, either after ops.repetition_penalty when
-one is set (one synchronisation per step, as in HF generate).  A prompt that emits eos or reaches max_new_tokens leaves the batch and
-its pages return to the free list.  hf_generation_kwargs turns HF generate() keyword arguments and the model's generation_config into
-packed_generate's.
-packed_generate(graph=True) keeps the decode loop on the device: the LLM step is replayed from a captured graph, the
-token bookkeeping is one ops.decode_advance launch per step, and the host reads a four-word status `lookahead` steps behind instead of
-the tokens.  DecodeGraphs keeps the captured graphs between calls.
+one is set (_selector, the one selector of both decode loops; one synchronisation per step, as in HF generate).  A prompt that emits
+eos or reaches max_new_tokens leaves the batch and its pages return to the free list.  hf_generation_kwargs turns HF generate() keyword
+arguments and the model's generation_config into packed_generate's.
+packed_generate(graph=True) keeps the decode loop on the device (_graph_decode): the LLM step is replayed from a captured
+graph, the token bookkeeping is one ops.decode_advance launch per step, and the host reads a four-word status `lookahead` steps behind
+instead of the tokens.  DecodeGraphs keeps the captured graphs between calls.
 """
 from __future__ import annotations
 
@@ -139,9 +139,7 @@ class DecodeGraphs:
     counts the graphs captured so far and `capture_ms` the time spent on them (warm-up forward + capture), so a caller can see reuse."""
 
     def __init__(self, model, pool: PagedKVPool, max_pages_per_prompt: int):
-        if isinstance(max_pages_per_prompt, bool) or not isinstance(max_pages_per_prompt, int) or max_pages_per_prompt < 1:
-            raise ValueError(f"max_pages_per_prompt must be an int >= 1, got {max_pages_per_prompt!r}")
-        self.model, self.pool, self.max_pages_per_prompt = model, pool, max_pages_per_prompt
+        self.model, self.pool, self.max_pages_per_prompt = model, pool, ops._int_in("max_pages_per_prompt", max_pages_per_prompt, 1)
         self.captures, self.capture_ms = 0, 0.0
         self.stream = None
         self._steps, self._rings = {}, {}
@@ -181,10 +179,97 @@ def _capture(graphs: DecodeGraphs, sg: _StepGraph, model, lm) -> None:
     graphs.capture_ms += (time.perf_counter() - t0) * 1e3
 
 
-def _graph_decode(model, lm, graphs: DecodeGraphs, logits, step_pos, seqlens, bt, max_new_tokens: int, lookahead: int, eos, select,
+def _selector(do_sample: bool, temperature, top_p, top_k, seed, repetition_penalty, sets):
+    """The token selector of both decode loops: select(logits [n, V], step, prev_tokens, row_ids) -> int64 [n] tokens (-1: invalid row).
+    sets: the penalty's token sets, or None without a penalty; row_ids: the prompt index of each row (the sampler's row id, the penalty's
+    token set), None when neither is on; prev_tokens: the last step's tokens, which join the sets at this step (None at step 0)."""
+    def select(logits, step, prev_tokens, row_ids):
+        if sets is not None and do_sample:
+            pen = ops.repetition_penalty(logits, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prev_tokens)
+            return ops.sample_tokens(pen, temperature, top_p, top_k, seed, row_ids=row_ids, step=step)
+        if sets is not None:
+            return ops.repetition_penalty(logits, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prev_tokens, return_tokens=True)
+        if do_sample:
+            return ops.sample_tokens(logits, temperature, top_p, top_k, seed, row_ids=row_ids, step=step)
+        return logits.argmax(-1)
+    return select
+
+
+def _prefill(model, lm, state: PagedState, p, bt):
+    """The packed prompts through the LLM; each layer also appends its keys / values, token t into row prompt(t) of the block table bt
+    at its position.  -> (logits [B, V] of each prompt's last token, step_pos [3, B]: the next token's M-RoPE position)"""
+    emb, pos, cu, lengths, max_len = p["inputs_embeds"], p["position_ids"], p["cu_seqlens"], p["lengths"], p["max_len"]
+    dev = emb.device
+    state.mode = "prefill"
+    state.tok_table = bt.index_select(0, _h2d([b for b, L in enumerate(lengths) for _ in range(L)], torch.int64, dev))
+    state.tok_pos = _h2d([i for L in lengths for i in range(L)], torch.int32, dev)
+    hidden = lm(inputs_embeds=emb[None], position_ids=pos[:, None, :], use_cache=False, cu_seq_lens_q=cu, cu_seq_lens_k=cu,
+                max_length_q=max_len, max_length_k=max_len, vsel_paged=state).last_hidden_state[0]
+    last = cu[1:].to(torch.int64) - 1
+    logits = model.lm_head(hidden[last])
+    state.tok_table = state.tok_pos = None
+    return logits, pos[:, last] + 1
+
+
+def _eager_decode(model, lm, state: PagedState, pages, lengths, logits, step_pos, seqlens, bt, max_new_tokens: int, eos, select, row_ids,
                   return_logits: bool):
+    """The host-driven decode loop: every step is an eager forward over the active rows and the host reads the step's tokens.  logits,
+    step_pos, seqlens, bt, select, row_ids as in _graph_decode; pages: each prompt's pages, which hold its `lengths` prompt keys.  A row
+    that crosses a page boundary draws one page; a prompt that emits eos or reaches max_new_tokens leaves the batch and its pages go
+    back to the pool at once (pages[b] is emptied).  -> (tokens, per-step logits or None)"""
+    pool, dev, n = state.pool, logits.device, len(lengths)
+    active = list(range(n))
+    lens = list(lengths)
+    tokens = [[] for _ in range(n)]
+    step_logits = [[] for _ in range(n)]
+    embed = model.get_input_embeddings()
+    prev = None
+    state.mode = "decode"
+    step = 0
+    while True:
+        nxt = select(logits, step, prev, row_ids)
+        host = nxt.tolist()                                       # the one host synchronisation of a step
+        keep = []
+        for i, b in enumerate(active):
+            if host[i] < 0:
+                raise RuntimeError(f"sampling failed for prompt {b} at step {step}: {_INVALID_LOGITS}")
+            tokens[b].append(host[i])
+            if return_logits:
+                step_logits[b].append(logits[i])
+            if host[i] in eos or len(tokens[b]) >= max_new_tokens:
+                pool.release(pages[b])                            # the prompt leaves the batch
+                pages[b] = []
+            else:
+                keep.append(i)
+        if not keep:
+            return tokens, step_logits if return_logits else None
+        if len(keep) < len(active):
+            idx = _h2d(keep, torch.int64, dev)
+            nxt, bt, step_pos, seqlens = nxt[idx], bt[idx], step_pos[:, idx], seqlens[idx]
+            if row_ids is not None:
+                row_ids = row_ids[idx]
+            active = [active[i] for i in keep]
+        for i, b in enumerate(active):                            # this step appends position lens[b]
+            need = _cdiv(lens[b] + 1, pool.page_size)
+            if need > len(pages[b]):
+                pages[b] += pool.alloc(1)
+                bt[i, need - 1] = pages[b][-1]
+        prev = nxt
+        state.block_table, state.cache_seqlens = bt, seqlens
+        hidden = lm(inputs_embeds=embed(nxt)[None], position_ids=step_pos[:, None, :], use_cache=False,
+                    vsel_paged=state).last_hidden_state[0]
+        logits = model.lm_head(hidden)
+        for b in active:
+            lens[b] += 1
+        seqlens = seqlens + 1
+        step_pos = step_pos + 1
+        step += 1
+
+
+def _graph_decode(model, lm, graphs: DecodeGraphs, logits, step_pos, seqlens, bt, max_new_tokens: int, lookahead: int, eos, select,
+                  row_ids, return_logits: bool):
     """The device-resident decode loop.  logits [n, V]: the prefill's; step_pos [3, n], seqlens int32 [n], bt int32 [n, width]: the
-    state of the first decode step; select(logits, step, prev) -> int64 [n] tokens (-1: invalid row).  Per step the host enqueues the
+    state of the first decode step; select, row_ids: _selector's, rows = prompts throughout.  Per step the host enqueues the
     selector, ops.decode_advance, a copy of its status into a pinned ring slot with an event, and the graph replay; before step s it
     reads the status of step s - lookahead.  Rows never leave the batch: decode_advance freezes a finished row, and later replays rewrite
     one cache slot of that row's own pages with the same values.  -> (tokens, per-step logits or None)"""
@@ -222,7 +307,7 @@ def _graph_decode(model, lm, graphs: DecodeGraphs, logits, step_pos, seqlens, bt
                     if status_of(step - lookahead) == 0:
                         break
                 # every row starts at step 0 together, so the loop index is the step of every active row
-                nxt = select(logits, step, sg.feed if step else None)
+                nxt = select(logits, step, sg.feed if step else None, row_ids)
                 if return_logits:
                     kept_logits.append(logits if step == 0 else logits.clone())
                 ops.decode_advance(nxt, eos_d, max_new_tokens, sg.done, sg.n_tokens, sg.state.cache_seqlens, sg.pos, sg.feed, tokens_out,
@@ -271,8 +356,7 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
         raise ValueError("max_new_tokens must be >= 1")
     if not isinstance(graph, (bool, DecodeGraphs)):
         raise TypeError(f"graph must be a bool or a DecodeGraphs, got {graph!r}")
-    if isinstance(lookahead, bool) or not isinstance(lookahead, int) or lookahead < 1:
-        raise ValueError(f"lookahead must be an int >= 1, got {lookahead!r}")
+    ops._int_in("lookahead", lookahead, 1)
     if isinstance(graph, DecodeGraphs):
         if graph.model is not model or (pool is not None and pool is not graph.pool):
             raise ValueError("this DecodeGraphs was built for another model / pool")
@@ -286,12 +370,12 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
     lm = model.model.language_model
     # the token sets of the penalty: every prompt id as passed (range-checked on the host before any device work)
     sets = ops.token_sets(input_ids, model.lm_head.out_features, model.lm_head.weight.device) if penalize else None
+    select = _selector(do_sample, temperature, top_p, top_k, seed, repetition_penalty, sets)
     register_paged_attention()
     p = _packed_inputs(model, input_ids, pixel_values, image_grid_thw, images_per_prompt, budgets)
-    emb, pos, cu, lengths = p["inputs_embeds"], p["position_ids"], p["cu_seqlens"], p["lengths"]
-    dev, n = emb.device, len(lengths)
-    attn0 = lm.layers[0].self_attn
-    hkv, hd = lm.config.num_key_value_heads, attn0.head_dim
+    lengths = p["lengths"]
+    dev, n = p["inputs_embeds"].device, len(lengths)
+    hkv, hd = lm.config.num_key_value_heads, lm.layers[0].self_attn.head_dim
     # the last new token is never fed back: a prompt holds at most L + max_new_tokens - 1 keys
     most = [_cdiv(L + max_new_tokens - 1, page_size) for L in lengths]
     if pool is None:
@@ -317,89 +401,16 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
             for b, L in enumerate(lengths):
                 pages[b] = pool.alloc(_cdiv(L, page_size))
         bt = _h2d([pg + [-1] * (width - len(pg)) for pg in pages], torch.int32, dev)
-        # prefill: the packed prompts through the LLM; each layer also appends its keys / values, token t into row
-        # prompt(t) of the block table at its position
-        state.mode = "prefill"
-        state.tok_table = bt.index_select(0, _h2d([b for b, L in enumerate(lengths) for _ in range(L)], torch.int64, dev))
-        state.tok_pos = _h2d([i for L in lengths for i in range(L)], torch.int32, dev)
         lm.config._attn_implementation = ATTN_NAME_PAGED
-        max_len = p["max_len"]
-        hidden = lm(inputs_embeds=emb[None], position_ids=pos[:, None, :], use_cache=False, cu_seq_lens_q=cu, cu_seq_lens_k=cu,
-                    max_length_q=max_len, max_length_k=max_len, vsel_paged=state).last_hidden_state[0]
-        last = cu[1:].to(torch.int64) - 1
-        logits = model.lm_head(hidden[last])
-        first_logits = logits
-        state.tok_table = state.tok_pos = None
-        step_pos = pos[:, last] + 1                                   # [3, B]: the next token's M-RoPE position
-        active = list(range(n))
-        lens = list(lengths)
-        tokens = [[] for _ in range(n)]
-        step_logits = [[] for _ in range(n)]
-        seqlens = _h2d(lens, torch.int32, dev)
-        embed = model.get_input_embeddings()
-        # the prompt index of each active row (the sampler's row id, the penalty's token set)
+        first_logits, step_pos = _prefill(model, lm, state, p, bt)
+        seqlens = _h2d(lengths, torch.int32, dev)
         row_ids = torch.arange(n, dtype=torch.int64, device=dev) if do_sample or penalize else None
-        prev = None                                                   # the last step's tokens, which join the sets at this step
-        state.mode = "decode"
-        step = 0
         if graphs is not None:
-            def select(lg, at, prv):                                  # the eager loop's selector launches, rows = prompts throughout
-                if penalize and do_sample:
-                    pen = ops.repetition_penalty(lg, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prv)
-                    return ops.sample_tokens(pen, temperature, top_p, top_k, seed, row_ids=row_ids, step=at)
-                if penalize:
-                    return ops.repetition_penalty(lg, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prv, return_tokens=True)
-                if do_sample:
-                    return ops.sample_tokens(lg, temperature, top_p, top_k, seed, row_ids=row_ids, step=at)
-                return lg.argmax(-1)
-            tokens, step_logits = _graph_decode(model, lm, graphs, logits, step_pos, seqlens, bt, max_new_tokens, lookahead, eos, select,
-                                                return_logits)
-        while graphs is None:
-            if penalize and do_sample:
-                pen = ops.repetition_penalty(logits, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prev)
-                nxt = ops.sample_tokens(pen, temperature, top_p, top_k, seed, row_ids=row_ids, step=step)
-            elif penalize:
-                nxt = ops.repetition_penalty(logits, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prev, return_tokens=True)
-            elif do_sample:
-                nxt = ops.sample_tokens(logits, temperature, top_p, top_k, seed, row_ids=row_ids, step=step)
-            else:
-                nxt = logits.argmax(-1)
-            host = nxt.tolist()                                       # the one host synchronisation of a step
-            keep = []
-            for i, b in enumerate(active):
-                if host[i] < 0:
-                    raise RuntimeError(f"sampling failed for prompt {b} at step {step}: {_INVALID_LOGITS}")
-                tokens[b].append(host[i])
-                if return_logits:
-                    step_logits[b].append(logits[i])
-                if host[i] in eos or len(tokens[b]) >= max_new_tokens:
-                    pool.release(pages[b])                            # the prompt leaves the batch
-                    pages[b] = []
-                else:
-                    keep.append(i)
-            if not keep:
-                break
-            if len(keep) < len(active):
-                idx = _h2d(keep, torch.int64, dev)
-                nxt, bt, step_pos, seqlens = nxt[idx], bt[idx], step_pos[:, idx], seqlens[idx]
-                if row_ids is not None:
-                    row_ids = row_ids[idx]
-                active = [active[i] for i in keep]
-            for i, b in enumerate(active):                            # this step appends position lens[b]
-                need = _cdiv(lens[b] + 1, page_size)
-                if need > len(pages[b]):
-                    pages[b] += pool.alloc(1)
-                    bt[i, need - 1] = pages[b][-1]
-            prev = nxt
-            state.block_table, state.cache_seqlens = bt, seqlens
-            hidden = lm(inputs_embeds=embed(nxt)[None], position_ids=step_pos[:, None, :], use_cache=False,
-                        vsel_paged=state).last_hidden_state[0]
-            logits = model.lm_head(hidden)
-            for b in active:
-                lens[b] += 1
-            seqlens = seqlens + 1
-            step_pos = step_pos + 1
-            step += 1
+            tokens, step_logits = _graph_decode(model, lm, graphs, first_logits, step_pos, seqlens, bt, max_new_tokens, lookahead, eos, select,
+                                                row_ids, return_logits)
+        else:
+            tokens, step_logits = _eager_decode(model, lm, state, pages, lengths, first_logits, step_pos, seqlens, bt, max_new_tokens, eos,
+                                                select, row_ids, return_logits)
     finally:
         lm.config._attn_implementation = old_impl
         for pg in pages:

@@ -67,6 +67,25 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _int_in(name: str, x, lo: int, hi: Optional[int] = None) -> int:
+    """x when it is an int, not a bool, in [lo, hi) (hi: a power of two, or None for no upper bound); ValueError otherwise."""
+    if isinstance(x, bool) or not isinstance(x, int) or x < lo or (hi is not None and x >= hi):
+        rng = f">= {lo}" if hi is None else f"in [{lo}, 2^{hi.bit_length() - 1})"
+        raise ValueError(f"{name} must be an int {rng}, got {x!r}")
+    return x
+
+
+def _logit_rows(logits: torch.Tensor) -> Tuple[int, int, int, int]:
+    """logits [batch, vocab] (bf16 / fp32, any row stride, contiguous columns) -> dtype code, batch, vocab, row stride."""
+    if logits.dim() != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
+        raise ValueError(f"logits must be [batch, vocab] with contiguous columns, got {tuple(logits.shape)} strides {logits.stride()}")
+    code = _code(logits)
+    b, v = logits.shape
+    if v < 1:
+        raise ValueError("empty vocabulary")
+    return code, b, v, logits.stride(0) if b > 1 else v
+
+
 def _scorer(wq, bq, wk, bk) -> N.Scorer:
     hd, d = wq.shape
     if wk.shape != (hd, d) or bq.shape != (hd,) or bk.shape != (hd,):
@@ -931,11 +950,7 @@ def check_sampling_args(temperature, top_p, top_k, seed) -> Tuple[float, float, 
         raise ValueError(f"temperature must be finite and > 0 (as float32), got {temperature!r}")
     if not (0.0 < float(top_p) <= 1.0 and p > 0):
         raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
-    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
-        raise ValueError(f"top_k must be an int >= 0, got {top_k!r}")
-    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
-        raise ValueError(f"seed must be an int in [0, 2^64), got {seed!r}")
-    return t, p, top_k, seed
+    return t, p, _int_in("top_k", top_k, 0), _int_in("seed", seed, 0, 2 ** 64)
 
 
 def sample_tokens(logits: torch.Tensor, temperature: float, top_p: float = 1.0, top_k: int = 0, seed: int = 0,
@@ -946,20 +961,13 @@ def sample_tokens(logits: torch.Tensor, temperature: float, top_p: float = 1.0, 
     its row id and step.  No host synchronisation.  -> int64 [B] (-1 for a row with a NaN / +inf or no finite logit), and with
     return_kept also int32 [B], the size of each row's kept set."""
     dev = _dev(logits, row_ids, strided_ok=True)
-    if logits.dim() != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
-        raise ValueError(f"logits must be [batch, vocab] with contiguous columns, got {tuple(logits.shape)} strides {logits.stride()}")
-    code = _code(logits)
+    code, b, v, stride = _logit_rows(logits)
     t, p, top_k, seed = check_sampling_args(temperature, top_p, top_k, seed)
-    if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < 2 ** 64:
-        raise ValueError(f"step must be an int in [0, 2^64), got {step!r}")
-    b, v = logits.shape
-    if v < 1:
-        raise ValueError("empty vocabulary")
+    _int_in("step", step, 0, 2 ** 64)
     if row_ids is not None:
         if row_ids.dtype != torch.int64 or row_ids.shape != (b,):
             raise TypeError(f"row_ids must be int64 [{b}]")
         row_ids = row_ids.contiguous()
-    stride = logits.stride(0) if b > 1 else v
     tokens = torch.empty(b, dtype=torch.int64, device=dev)
     kept = torch.empty(b, dtype=torch.int32, device=dev) if return_kept else None
     N.check(N.lib().vsel_sample_tokens(_stream(), logits.data_ptr(), code, b, v, stride, t, p, top_k, seed, _p(row_ids), step,
@@ -1016,13 +1024,8 @@ def repetition_penalty(logits: torch.Tensor, penalty: float, sets: torch.Tensor,
     -> y fp32 [B, V] (written into `out` when given); return_tokens=True: the greedy tokens int64 [B] = argmax(y) instead, without an fp32
     row unless `out` is given too, then (out, tokens)."""
     dev = _dev(logits, sets, row_ids, prev_tokens, out, strided_ok=True)
-    if logits.dim() != 2 or (logits.shape[1] > 1 and logits.stride(1) != 1):
-        raise ValueError(f"logits must be [batch, vocab] with contiguous columns, got {tuple(logits.shape)} strides {logits.stride()}")
-    code = _code(logits)
+    code, b, v, stride = _logit_rows(logits)
     p = check_repetition_penalty(penalty)
-    b, v = logits.shape
-    if v < 1:
-        raise ValueError("empty vocabulary")
     if sets.dtype != torch.int32 or sets.dim() != 2 or sets.shape[1] != (v + 31) // 32 or not sets.is_contiguous():
         raise ValueError(f"sets must be contiguous int32 [n_sets, {(v + 31) // 32}] (token_sets for vocab {v}), got {sets.dtype} "
                          f"{tuple(sets.shape)}")
@@ -1034,7 +1037,6 @@ def repetition_penalty(logits: torch.Tensor, penalty: float, sets: torch.Tensor,
     if out is None and not return_tokens:
         out = torch.empty(b, v, dtype=torch.float32, device=dev)
     tokens = torch.empty(b, dtype=torch.int64, device=dev) if return_tokens else None
-    stride = logits.stride(0) if b > 1 else v
     N.check(N.lib().vsel_repetition_penalty(_stream(), logits.data_ptr(), code, b, v, stride, p, sets.data_ptr(), sets.shape[0],
                                             _p(row_ids), _p(prev_tokens), _p(tokens), _p(out)))
     if not return_tokens:
@@ -1049,8 +1051,7 @@ def decode_advance(next_tokens: torch.Tensor, eos: Optional[torch.Tensor], max_n
     logits), n_tokens int32 [B], cache_seqlens int32 [B], pos int32 / int64 [3, B], feed int64 [B], tokens_out int64 [B, max_new_tokens],
     status int32 [4] = {rows still active, lowest row that turned invalid in this launch or -1, its n_tokens or -1, 0}.  All contiguous.
     One launch, no allocation, no host synchronisation: capturable.  Shapes and dtypes are checked before any device work."""
-    if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
-        raise ValueError(f"max_new_tokens must be an int >= 1, got {max_new_tokens!r}")
+    _int_in("max_new_tokens", max_new_tokens, 1)
     if next_tokens.dtype != torch.int64 or next_tokens.dim() != 1:
         raise TypeError("next_tokens must be int64 [B]")
     b = next_tokens.shape[0]
