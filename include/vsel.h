@@ -434,6 +434,33 @@ int vsel_decode_advance(void* stream, const int64_t* next, int64_t batch, const 
                         int32_t* done, int32_t* n_tokens, int32_t* cache_seqlens, void* pos, int pos_is_int64, int64_t* feed,
                         int64_t* tokens_out, int32_t* status);
 
+/* -------- fused LM cross-entropy: per-token log-probabilities of given tokens, and their gradient (the reference computes the LM loss
+ * in torch: logits.float(), shift, CrossEntropyLoss, qwen-vl-finetune/compression_method/selector_model.py:293-305,
+ * llava-ov-15/compression_method/selector_model.py:353) ------------------------------------------------------------------
+ * vsel_token_logprob_fwd: logits DEVICE [rows, vocab] bf16 | f32, row_stride in elements (any value >= vocab; rows may start at any
+ * element); targets DEVICE int64 [rows].  Row r with t = targets[r]: t == ignore_index -> logprob[r] = lse[r] = 0 and the row's logits
+ * are not read; t outside [0, vocab) -> logprob[r] = lse[r] = NaN, the logits are not read either (never an access outside the row,
+ * never a device assert); else lse[r] = log sum_j exp(x_j) and logprob[r] = x_t - lse[r], fp32 arithmetic with the max subtracted, the
+ * row sum and the last step in fp64, each output rounded once.  -inf entries are legal (a target on -inf gives -inf); a row with a
+ * NaN, a +inf or no finite entry gives NaN.  A row's bits depend on that row's logits and target alone (not on rows, its position or
+ * the other rows); reruns are bit-identical; no float atomics.  sum_out (DEVICE float[1], or NULL) = the sum of logprob over all rows
+ * in this fixed order, a rule of rows alone: p_i = sum over k of logprob[i + 1024 k], k ascending, in fp64 (i = 0..1023), then
+ * p_i += p_{i + h} for i < h, h = 512, 256, ... 1, in fp64; sum_out = (float)p_0.  n_valid_out (DEVICE int32[1], or NULL) = the rows
+ * whose target is not ignore_index.  logprob, lse DEVICE float [rows].
+ * vsel_token_logprob_bwd: grad_logits DEVICE [rows, vocab] contiguous, dtype of logits, overwritten.  Row r with a target in [0, vocab):
+ * grad_logits[r, j] = c_r ([j == t] - exp(x_j - lse[r])), c_r = (grad_rows ? grad_rows[r] : 1) * (grad_scale ? grad_scale[0] : 1), both
+ * DEVICE float (nothing is read on the host); fp32 arithmetic for bf16 rows, fp64 for f32 rows, one rounding to the output dtype.
+ * Every other row (ignored, or target out of range) is written as zeros and its logits are not read.
+ * Both: element offsets are 64-bit (rows * row_stride may exceed 2^31); no workspace; no host synchronisation.  VSEL_ERR_INVALID for
+ * NULL logits / targets / logprob / lse / grad_logits, rows < 0, vocab < 1, row_stride < vocab; VSEL_ERR_UNSUPPORTED for
+ * vocab >= 2^31 or rows >= 2^31 -- all checked before any HIP call.  rows == 0 writes sum_out = 0 and n_valid_out = 0, nothing else.  */
+int vsel_token_logprob_fwd(void* stream, const void* logits, vsel_dtype dtype, int64_t rows, int64_t vocab, int64_t row_stride,
+                           const int64_t* targets, int64_t ignore_index, float* logprob, float* lse, float* sum_out,
+                           int32_t* n_valid_out);
+int vsel_token_logprob_bwd(void* stream, const void* logits, vsel_dtype dtype, int64_t rows, int64_t vocab, int64_t row_stride,
+                           const int64_t* targets, int64_t ignore_index, const float* lse, const float* grad_rows,
+                           const float* grad_scale, void* grad_logits);
+
 /* -------- the same forward with a caller workspace: key-range parts for ONE long sequence ------------------------
  * vsel_varlen_attn_fwd (and _lse when lse != NULL) on batches the launch cannot balance as they are -- one uncompressed prompt, or a
  * few of equal length: 256-query items cut over key ranges, fp32 partial outputs + (m, l) in `ws`, merged in part order by a second

@@ -81,6 +81,8 @@ SIGNATURES = {
     "vsel_token_sets_build": (C.c_int, [_P, _P, _P, _I64, _I64, _P]),
     "vsel_repetition_penalty": (C.c_int, [_P, _P, C.c_int, _I64, _I64, _I64, C.c_double, _P, _I64, _P, _P, _P, _P]),
     "vsel_decode_advance": (C.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    "vsel_token_logprob_fwd": (C.c_int, [_P, _P, C.c_int, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _P]),
+    "vsel_token_logprob_bwd": (C.c_int, [_P, _P, C.c_int, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _P]),
 }
 
 # include/vsel_debug.h (diagnostic knobs; not part of the drop-in boundary)

@@ -27,6 +27,7 @@ from transformers.utils import ModelOutput
 
 from . import ops
 from .hf_generic import make_vision_tower_forward_selector
+from .loss import use_fused_lm_loss
 from .selector import TransformerScorer
 
 
@@ -197,8 +198,9 @@ def llavaov15_generation_forward_selector(self, input_ids=None, attention_mask=N
 
 
 def install_selector_llavaov15(model, budget: float, in_features: Optional[int] = None, hidden_dim: Optional[int] = None,
-                               regularization_weight: float = 0.1):
-    """What train_sft_visionselector.py:219-225 does: attach the scorer and bind the three training forwards."""
+                               regularization_weight: float = 0.1, fused_lm_loss: bool = False):
+    """What train_sft_visionselector.py:219-225 does: attach the scorer and bind the three training forwards.
+    fused_lm_loss=True also makes model.loss_function the fused HIP cross-entropy (loss.use_fused_lm_loss)."""
     vl = model.model
     visual = vl.visual
     p = next(visual.parameters())
@@ -209,6 +211,8 @@ def install_selector_llavaov15(model, budget: float, in_features: Optional[int] 
     vl.forward = types.MethodType(llavaov15_vlmodel_forward_selector, vl)
     model.forward = types.MethodType(llavaov15_generation_forward_selector, model)
     model.regularization_weight = regularization_weight
+    if fused_lm_loss:
+        use_fused_lm_loss(model)
     return model
 
 

@@ -20,6 +20,7 @@ from transformers.models.qwen2_5_vl import modeling_qwen2_5_vl as hf
 
 from . import ops
 from .hf_generic import make_vision_tower_forward_selector, select_and_splice, select_block_from_tokens
+from .loss import use_fused_lm_loss
 from .selector import TransformerScorer
 
 _BaseTower = hf.Qwen2_5_VisionTransformerPretrainedModel
@@ -72,8 +73,9 @@ def qwen25vl_generation_forward_selector(self, input_ids=None, attention_mask=No
 
 
 def install_selector(model, budget: float, in_features: Optional[int] = None, hidden_dim: Optional[int] = None,
-                     regularization_weight: float = 0.1):
-    """What train_qwen_selector.py:190-200 does, for a stock transformers model: attach the scorer, bind the two forwards."""
+                     regularization_weight: float = 0.1, fused_lm_loss: bool = False):
+    """What train_qwen_selector.py:190-200 does, for a stock transformers model: attach the scorer, bind the two forwards.
+    fused_lm_loss=True also makes model.loss_function the fused HIP cross-entropy (loss.use_fused_lm_loss)."""
     visual = _visual_of(model)
     d = in_features or visual.config.out_hidden_size
     visual.budgets = budget
@@ -82,6 +84,8 @@ def install_selector(model, budget: float, in_features: Optional[int] = None, hi
     visual.forward = types.MethodType(qwen25vl_vision_tower_forward_selector, visual)
     model.forward = types.MethodType(qwen25vl_generation_forward_selector, model)
     model.regularization_weight = regularization_weight
+    if fused_lm_loss:
+        use_fused_lm_loss(model)
     return model
 
 

@@ -1071,8 +1071,80 @@ def decode_advance(next_tokens: torch.Tensor, eos: Optional[torch.Tensor], max_n
                                         int(pos.dtype == torch.int64), feed.data_ptr(), tokens_out.data_ptr(), status.data_ptr()))
 
 
+def _logprob_args(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int):
+    dev = _dev(logits, targets, strided_ok=True)
+    code, rows, v, stride = _logit_rows(logits)
+    if targets.dtype != torch.int64 or targets.shape != (rows,) or not targets.is_contiguous():
+        raise TypeError(f"targets must be contiguous int64 [{rows}], got {targets.dtype} {tuple(targets.shape)}")
+    return dev, code, rows, v, stride, _int_in("ignore_index", ignore_index, -2 ** 63, 2 ** 63)
+
+
+def token_logprob_fwd(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100, reduce: bool = False):
+    """vsel_token_logprob_fwd without autograd: logits [rows, V] (bf16 / fp32, any row stride, contiguous columns), targets int64 [rows]
+    -> logprob fp32 [rows] (x_t - lse; 0 for a row whose target is ignore_index, NaN for a target outside [0, V)) and lse fp32 [rows];
+    with reduce=True also sum fp32 [1] (the fixed-order sum of logprob, include/vsel.h) and n_valid int32 [1].  Ignored rows are not read.
+    No host synchronisation."""
+    dev, code, rows, v, stride, ign = _logprob_args(logits, targets, ignore_index)
+    logprob = torch.empty(rows, dtype=torch.float32, device=dev)
+    lse = torch.empty(rows, dtype=torch.float32, device=dev)
+    total = torch.empty(1, dtype=torch.float32, device=dev) if reduce else None
+    n_valid = torch.empty(1, dtype=torch.int32, device=dev) if reduce else None
+    # (tensors without elements have no address: rows == 0 passes a pointer that is never followed)
+    none = torch.empty(1, dtype=torch.float32, device=dev).data_ptr() if rows == 0 else 0
+    N.check(N.lib().vsel_token_logprob_fwd(_stream(), logits.data_ptr() or none, code, rows, v, stride, targets.data_ptr() or none, ign,
+                                           logprob.data_ptr() or none, lse.data_ptr() or none, _p(total), _p(n_valid)))
+    return (logprob, lse, total, n_valid) if reduce else (logprob, lse)
+
+
+def token_logprob_bwd(logits: torch.Tensor, targets: torch.Tensor, lse: torch.Tensor, grad_rows: Optional[torch.Tensor] = None,
+                      grad_scale: Optional[torch.Tensor] = None, ignore_index: int = -100) -> torch.Tensor:
+    """vsel_token_logprob_bwd: grad_logits [rows, V] contiguous in logits' dtype, row r = c_r ([j == t] - exp(x_j - lse[r])) with
+    c_r = grad_rows[r] (fp32 [rows], default 1) * grad_scale[0] (fp32 [1], default 1), both read on the device; zeros for ignored rows
+    and rows whose target is outside [0, V) (their logits are not read).  One rounding to the output dtype."""
+    dev, code, rows, v, stride, ign = _logprob_args(logits, targets, ignore_index)
+    for name, t, shape in (("lse", lse, (rows,)), ("grad_rows", grad_rows, (rows,)), ("grad_scale", grad_scale, (1,))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise TypeError(f"{name} must be contiguous float32 {list(shape)}, got {t.dtype} {list(t.shape)}")
+    _dev(lse, grad_rows, grad_scale)
+    grad = torch.empty(rows, v, dtype=logits.dtype, device=dev)
+    if rows == 0:
+        return grad
+    N.check(N.lib().vsel_token_logprob_bwd(_stream(), logits.data_ptr(), code, rows, v, stride, targets.data_ptr(), ign, lse.data_ptr(),
+                                           _p(grad_rows), _p(grad_scale), grad.data_ptr()))
+    return grad
+
+
+class _TokenLogprobs(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, ignore_index):
+        logprob, lse = token_logprob_fwd(logits, targets, ignore_index)
+        ctx.save_for_backward(logits, targets, lse)
+        ctx.ignore_index = ignore_index
+        ctx.set_materialize_grads(False)
+        return logprob, lse
+
+    @staticmethod
+    def backward(ctx, g_logprob, g_lse):
+        if g_lse is not None:
+            raise RuntimeError("token_logprobs: lse is returned for reuse, not for differentiation (a gradient reached it)")
+        if g_logprob is None:
+            return None, None, None
+        logits, targets, lse = ctx.saved_tensors
+        g = g_logprob.to(torch.float32).contiguous()
+        return token_logprob_bwd(logits, targets, lse, grad_rows=g, ignore_index=ctx.ignore_index), None, None
+
+
+def token_logprobs(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100):
+    """Per-token log-probabilities of given tokens: logits [rows, V] (bf16 / fp32, any row stride, contiguous columns), targets int64
+    [rows] -> (logprob fp32 [rows], lse fp32 [rows]); see token_logprob_fwd.  Differentiable in logits (the gradient comes from
+    vsel_token_logprob_bwd, in logits' dtype, with the incoming gradient of logprob as the per-row factor); lse is not differentiable:
+    a gradient that reaches it raises in the backward."""
+    _logprob_args(logits, targets, ignore_index)
+    return _TokenLogprobs.apply(logits, targets, ignore_index)
+
+
 # every op that reaches libvsel switches to its tensors' device first
-for _name in ("lis_scores", "lis_select", "lis_select_permuted", "gelu_colsum", "colsum_linear", "lis_select_presummed", "lis_select_varlen",
+for _name in ("token_logprob_fwd", "token_logprob_bwd", "token_logprobs","lis_scores", "lis_select", "lis_select_permuted", "gelu_colsum", "colsum_linear", "lis_select_presummed", "lis_select_varlen",
               "hard_topk", "gather_rows", "soft_topk_fwd", "soft_topk_bwd", "lis_train_fwd", "lis_train_bwd", "lis_train_bwd_factors", "factors_to_grads", "lis_scores_bwd",
               "splice", "splice_batched", "lis_select_splice", "topk_select_splice", "varlen_attn", "varlen_attn_fwd_lse", "varlen_attn_bwd", "varlen_attn_kv",
               "attn_head_major", "paged_attn", "kvcache_attn", "sample_tokens", "token_sets", "repetition_penalty", "decode_advance"):

@@ -20,6 +20,7 @@ import torch
 import torch.distributed as dist
 
 from .ddp import LisFactorSync, LisGradSync
+from .loss import use_fused_lm_loss
 from .selector import curriculum_weight, factor_sink
 
 SCORER_KEY = "importance_scorer"
@@ -84,15 +85,19 @@ class LisTrainer:
     def __init__(self, model: torch.nn.Module, max_steps: int, lr: float = 5e-5, weight_decay: float = 0.0,
                  reg_weight_start: float = 0.1, reg_weight_end: float = 2.0, max_grad_norm: float = 1.0,
                  warmup_ratio: float = 0.03, group: Optional[dist.ProcessGroup] = None, log: Callable[[str], None] = print,
-                 logging_steps: int = 1, exchange: str = "dense"):
+                 logging_steps: int = 1, exchange: str = "dense", fused_lm_loss: bool = False):
         """exchange="dense": the scorer's fp32 gradients live in one flat bucket, ONE all-reduce per optimizer step
         (51.4 MB at 7B).  exchange="factors": every micro-batch's LIS backward leaves a 57 KB rank-1-factor payload row
         (selector.factor_sink), the step all-gathers the rows and every rank rebuilds the mean gradient itself
-        (ddp.LisFactorSync); same gradients to fp32 rounding, and no dense [Hd, D] write per micro-batch."""
+        (ddp.LisFactorSync); same gradients to fp32 rounding, and no dense [Hd, D] write per micro-batch.
+        fused_lm_loss=True: the model's LM loss and its gradient come from the fused HIP cross-entropy (loss.use_fused_lm_loss);
+        False leaves model.loss_function as it is."""
         if exchange not in ("dense", "factors"):
             raise ValueError("exchange must be 'dense' or 'factors'")
         self.exchange = exchange
         self.model = model
+        if fused_lm_loss:
+            use_fused_lm_loss(model)
         self.params = freeze_all_but_scorer(model)
         self.max_steps = max_steps
         self.reg_weight_start, self.reg_weight_end = reg_weight_start, reg_weight_end
