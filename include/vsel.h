@@ -396,6 +396,28 @@ int vsel_sample_tokens(void* stream, const void* logits, vsel_dtype dtype, int64
                        float temperature, float top_p, int64_t top_k, uint64_t seed, const int64_t* row_ids, uint64_t step,
                        int64_t* tokens, int32_t* kept);
 
+/* vsel_sample_tokens_rows: the same draw with the parameters of each row read from the device, plus greedy rows, min-p and the
+ * drawn token's log-probability ("per-row parameters").  temperature / top_p / min_p DEVICE float [batch], top_k
+ * DEVICE int32 [batch]; a NULL array switches that filter off for every row (temperature 1, top_p 1, top_k 0, min_p 0).  Row b:
+ *   temperature[b] == 0   greedy: token = argmax of the raw row (lowest index among equal values), kept 1, the row's other
+ *                         parameters ignored;
+ *   otherwise             vsel_sample_tokens' rules with c = (float)(log2(e) / (double)temperature[b]), then min-p (HF's
+ *                         MinPLogitsWarper, after top-k and top-p): an entry of the top-k / top-p set stays iff
+ *                         d = (x - m) * c >= (float)log2((double)min_p[b]) in fp32 (min_p 0: off; the row maximum always stays).
+ * kept DEVICE int32 [batch] or NULL: the size of the final set.  logprob DEVICE float [batch] or NULL: the log-probability of the
+ * token under the distribution it was drawn from, (double)d_t * ln2 - log(Z_kept * 2^-40) rounded once to fp32, Z_kept the
+ * integer sum of the fixed-point masses over the final set (bit-reproducible); for a greedy row the same at temperature 1 over all
+ * finite entries (the model's log-softmax; that extra pass over the row runs only with logprob != NULL).  A row with a NaN / +inf
+ * or no finite logit, and a row whose parameters are out of range (temperature < 0 or not finite, top_p outside (0, 1],
+ * top_k < 0, min_p outside [0, 1]) gives token -1, kept 0, logprob NaN; the other rows are unaffected and nothing is asserted on
+ * the device.  With equal parameters on every row and min_p 0, tokens and kept are bit for bit vsel_sample_tokens'.  One launch, no
+ * workspace, no host synchronisation, capturable.  VSEL_ERR_INVALID for NULL logits / tokens, batch < 0, vocab < 1,
+ * row_stride < vocab, a dtype other than bf16 / f32 -- all checked before any HIP call; VSEL_ERR_UNSUPPORTED for vocab >= 2^24.
+ * batch == 0 is a no-op.                                                                                                         */
+int vsel_sample_tokens_rows(void* stream, const void* logits, vsel_dtype dtype, int64_t batch, int64_t vocab, int64_t row_stride,
+                            const float* temperature, const float* top_p, const int32_t* top_k, const float* min_p, uint64_t seed,
+                            const int64_t* row_ids, uint64_t step, int64_t* tokens, int32_t* kept, float* logprob);
+
 /* -------- repetition penalty over per-prompt token sets (no reference kernel: HF generate() applies RepetitionPenaltyLogitsProcessor
  * whenever the merged generation config holds repetition_penalty != 1.0, greedy or sampled; the eval callers leave it to the
  * checkpoint's generation_config.json) ------------------------------------------------------------------------------------------------

@@ -78,6 +78,7 @@ SIGNATURES = {
                                         _I64, _P, _I64, _P, _P, _P, _P, C.c_int, _I64, _I64, C.c_int, _I64, _I64, _I64, _I64, _I64, _F,
                                         C.c_int, _P, _P, _P, _SZ]),
     "vsel_sample_tokens": (C.c_int, [_P, _P, C.c_int, _I64, _I64, _I64, _F, _F, _I64, _U64, _P, _U64, _P, _P]),
+    "vsel_sample_tokens_rows": (C.c_int, [_P, _P, C.c_int, _I64, _I64, _I64, _P, _P, _P, _P, _U64, _P, _U64, _P, _P, _P]),
     "vsel_token_sets_build": (C.c_int, [_P, _P, _P, _I64, _I64, _P]),
     "vsel_repetition_penalty": (C.c_int, [_P, _P, C.c_int, _I64, _I64, _I64, C.c_double, _P, _I64, _P, _P, _P, _P]),
     "vsel_decode_advance": (C.c_int, [_P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, C.c_int, _P, _P, _P]),

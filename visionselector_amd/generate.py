@@ -179,20 +179,47 @@ def _capture(graphs: DecodeGraphs, sg: _StepGraph, model, lm) -> None:
     graphs.capture_ms += (time.perf_counter() - t0) * 1e3
 
 
-def _selector(do_sample: bool, temperature, top_p, top_k, seed, repetition_penalty, sets):
-    """The token selector of both decode loops: select(logits [n, V], step, prev_tokens, row_ids) -> int64 [n] tokens (-1: invalid row).
+def _selector(do_sample: bool, temperature, top_p, top_k, seed, repetition_penalty, sets, rows=None, logprobs: bool = False):
+    """The token selector of both decode loops: select(logits [n, V], step, prev_tokens, row_ids) -> (int64 [n] tokens (-1: invalid row),
+    float32 [n] log-probabilities or None).
     sets: the penalty's token sets, or None without a penalty; row_ids: the prompt index of each row (the sampler's row id, the penalty's
-    token set), None when neither is on; prev_tokens: the last step's tokens, which join the sets at this step (None at step 0)."""
+    token set), None when neither is on; prev_tokens: the last step's tokens, which join the sets at this step (None at step 0).
+    rows None: one set of parameters for the call -- argmax, ops.sample_tokens or ops.repetition_penalty, the launches made before
+    per-prompt parameters existed.  rows: dict(temperature, top_p, top_k, min_p) of device arrays with one value per PROMPT (temperature
+    0: a greedy prompt) -> ops.sample_tokens_rows over the arrays' entries at row_ids, and with `logprobs` the tokens' log-probabilities."""
     def select(logits, step, prev_tokens, row_ids):
         if sets is not None and do_sample:
             pen = ops.repetition_penalty(logits, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prev_tokens)
-            return ops.sample_tokens(pen, temperature, top_p, top_k, seed, row_ids=row_ids, step=step)
+            return ops.sample_tokens(pen, temperature, top_p, top_k, seed, row_ids=row_ids, step=step), None
         if sets is not None:
-            return ops.repetition_penalty(logits, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prev_tokens, return_tokens=True)
+            return ops.repetition_penalty(logits, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prev_tokens, return_tokens=True), None
         if do_sample:
-            return ops.sample_tokens(logits, temperature, top_p, top_k, seed, row_ids=row_ids, step=step)
-        return logits.argmax(-1)
-    return select
+            return ops.sample_tokens(logits, temperature, top_p, top_k, seed, row_ids=row_ids, step=step), None
+        return logits.argmax(-1), None
+
+    if rows is None:
+        return select
+    n = rows["temperature"].shape[0]
+    active = {"ids": None, "rows": rows}
+
+    def select_rows(logits, step, prev_tokens, row_ids):
+        if row_ids is not active["ids"]:                 # the eager loop hands over a new row_ids when prompts have left the batch
+            active["ids"] = row_ids
+            active["rows"] = rows if row_ids.shape[0] == n else {k: v.index_select(0, row_ids) for k, v in rows.items()}
+        if sets is not None:
+            logits = ops.repetition_penalty(logits, repetition_penalty, sets, row_ids=row_ids, prev_tokens=prev_tokens)
+        out = ops.sample_tokens_rows(logits, seed=seed, row_ids=row_ids, step=step, return_logprobs=logprobs, **active["rows"])
+        return out if logprobs else (out, None)
+    return select_rows
+
+
+def _per_prompt(name: str, value, n: int):
+    """A packed_generate parameter given as one value or as a list / tuple with one value per prompt -> (n values, was a sequence)"""
+    if isinstance(value, (list, tuple)):
+        if len(value) != n:
+            raise ValueError(f"{name} holds {len(value)} values for {n} prompts")
+        return list(value), True
+    return [value] * n, False
 
 
 def _prefill(model, lm, state: PagedState, p, bt):
@@ -216,24 +243,28 @@ def _eager_decode(model, lm, state: PagedState, pages, lengths, logits, step_pos
     """The host-driven decode loop: every step is an eager forward over the active rows and the host reads the step's tokens.  logits,
     step_pos, seqlens, bt, select, row_ids as in _graph_decode; pages: each prompt's pages, which hold its `lengths` prompt keys.  A row
     that crosses a page boundary draws one page; a prompt that emits eos or reaches max_new_tokens leaves the batch and its pages go
-    back to the pool at once (pages[b] is emptied).  -> (tokens, per-step logits or None)"""
+    back to the pool at once (pages[b] is emptied).  -> (tokens, per-step logits or None, per-step log-probabilities or None)"""
     pool, dev, n = state.pool, logits.device, len(lengths)
     active = list(range(n))
     lens = list(lengths)
     tokens = [[] for _ in range(n)]
     step_logits = [[] for _ in range(n)]
+    logprobs = [[] for _ in range(n)]
     embed = model.get_input_embeddings()
     prev = None
     state.mode = "decode"
     step = 0
     while True:
-        nxt = select(logits, step, prev, row_ids)
+        nxt, lp = select(logits, step, prev, row_ids)
         host = nxt.tolist()                                       # the one host synchronisation of a step
+        lp_host = None if lp is None else lp.tolist()
         keep = []
         for i, b in enumerate(active):
             if host[i] < 0:
                 raise RuntimeError(f"sampling failed for prompt {b} at step {step}: {_INVALID_LOGITS}")
             tokens[b].append(host[i])
+            if lp_host is not None:
+                logprobs[b].append(lp_host[i])
             if return_logits:
                 step_logits[b].append(logits[i])
             if host[i] in eos or len(tokens[b]) >= max_new_tokens:
@@ -242,7 +273,7 @@ def _eager_decode(model, lm, state: PagedState, pages, lengths, logits, step_pos
             else:
                 keep.append(i)
         if not keep:
-            return tokens, step_logits if return_logits else None
+            return tokens, step_logits if return_logits else None, logprobs if lp_host is not None else None
         if len(keep) < len(active):
             idx = _h2d(keep, torch.int64, dev)
             nxt, bt, step_pos, seqlens = nxt[idx], bt[idx], step_pos[:, idx], seqlens[idx]
@@ -272,7 +303,9 @@ def _graph_decode(model, lm, graphs: DecodeGraphs, logits, step_pos, seqlens, bt
     state of the first decode step; select, row_ids: _selector's, rows = prompts throughout.  Per step the host enqueues the
     selector, ops.decode_advance, a copy of its status into a pinned ring slot with an event, and the graph replay; before step s it
     reads the status of step s - lookahead.  Rows never leave the batch: decode_advance freezes a finished row, and later replays rewrite
-    one cache slot of that row's own pages with the same values.  -> (tokens, per-step logits or None)"""
+    one cache slot of that row's own pages with the same values.  The selector's log-probabilities, when it returns them, go into column
+    `step` of a [n, max_new_tokens] device buffer that is read once after the loop.
+    -> (tokens, per-step logits or None, per-step log-probabilities or None)"""
     dev, n = logits.device, logits.shape[0]
     cur = torch.cuda.current_stream(dev)
     if graphs.stream is None:
@@ -282,6 +315,7 @@ def _graph_decode(model, lm, graphs: DecodeGraphs, logits, step_pos, seqlens, bt
     slots = lookahead + 1
     ring, events = graphs._ring(slots)
     kept_logits = []
+    lp_buf = None
 
     def status_of(step: int) -> int:
         events[step % slots].synchronize()
@@ -307,7 +341,11 @@ def _graph_decode(model, lm, graphs: DecodeGraphs, logits, step_pos, seqlens, bt
                     if status_of(step - lookahead) == 0:
                         break
                 # every row starts at step 0 together, so the loop index is the step of every active row
-                nxt = select(logits, step, sg.feed if step else None, row_ids)
+                nxt, lp = select(logits, step, sg.feed if step else None, row_ids)
+                if lp is not None:
+                    if lp_buf is None:
+                        lp_buf = torch.zeros(n, max_new_tokens, dtype=torch.float32, device=dev)
+                    lp_buf[:, step].copy_(lp)
                 if return_logits:
                     kept_logits.append(logits if step == 0 else logits.clone())
                 ops.decode_advance(nxt, eos_d, max_new_tokens, sg.done, sg.n_tokens, sg.state.cache_seqlens, sg.pos, sg.feed, tokens_out,
@@ -324,12 +362,14 @@ def _graph_decode(model, lm, graphs: DecodeGraphs, logits, step_pos, seqlens, bt
                 status_of(step)
             counts = sg.n_tokens.tolist()
             rows = tokens_out.tolist()
+            lp_rows = None if lp_buf is None else lp_buf.tolist()
     finally:
         s.synchronize()                             # also on an exception: nothing in flight writes pages that go back to the free list
         cur.wait_stream(s)
     tokens = [rows[b][:counts[b]] for b in range(n)]
     step_logits = [[kept_logits[i][b] for i in range(counts[b])] for b in range(n)] if return_logits else None
-    return tokens, step_logits
+    logprobs = None if lp_rows is None else [lp_rows[b][:counts[b]] for b in range(n)]
+    return tokens, step_logits, logprobs
 
 
 @torch.no_grad()
@@ -337,7 +377,7 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
                     images_per_prompt: Sequence[int], max_new_tokens: int, budgets: float | None = None, eos_token_id=None,
                     page_size: int = 64, pool: PagedKVPool | None = None, return_logits: bool = False, do_sample: bool = False,
                     temperature: float = 1.0, top_p: float = 1.0, top_k: int = 0, seed: int = 0, repetition_penalty: float = 1.0,
-                    graph=False, lookahead: int = DEFAULT_LOOKAHEAD):
+                    graph=False, lookahead: int = DEFAULT_LOOKAHEAD, min_p: float = 0.0, return_logprobs: bool = False):
     """Greedy or sampled generation for a batch of image prompts (arguments as packed_prefill).
     -> dict(tokens: B lists of new token ids (each ends at eos or after max_new_tokens), kept [B], first_logits [B, vocab]
             (bit-identical to packed_prefill's logits), pool, and with return_logits: logits, B lists of [vocab] per step).
@@ -348,6 +388,13 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
     top_p and seed, as HF's do_sample with those warpers; the draw of prompt b at its s-th new token uses row id b and
     step s, so it does not depend on the other prompts or on when they leave the batch.  A prompt whose logits hold a NaN / +inf
     (or no finite value) raises RuntimeError.
+    Per-prompt parameters: do_sample, temperature, top_p, top_k and min_p each take one value or a list / tuple with one value per prompt,
+    so a call can mix greedy and sampled prompts and different temperatures.  min_p (0: off) is HF's MinPLogitsWarper, applied after top-k
+    and top-p.  return_logprobs=True adds `logprobs`: B lists of floats aligned with `tokens`, the log-probability of each token under
+    the distribution it was drawn from (a greedy prompt: the log-softmax of its logits); with a repetition penalty that is the
+    distribution of the PENALISED logits.  A list, min_p != 0 or return_logprobs selects through ops.sample_tokens_rows (DESIGN.md §13,
+    "per-row parameters"), a prompt with do_sample False as a temperature-0 row; every other call makes the launches it made before these
+    arguments existed.
     graph=False: every decode step is an eager forward and the host reads the step's tokens.  graph=True, or a DecodeGraphs (which keeps
     the captured graph between calls and fixes the pool): the same tokens and logits from the device-resident loop of DESIGN.md §15 --
     every prompt holds all its pages from the start, finished prompts stay in the batch as frozen rows, and the host reads a status
@@ -361,16 +408,38 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
         if graph.model is not model or (pool is not None and pool is not graph.pool):
             raise ValueError("this DecodeGraphs was built for another model / pool")
         pool = graph.pool
-    if not isinstance(do_sample, bool):
-        raise TypeError(f"do_sample must be a bool, got {do_sample!r}")
-    if do_sample:
-        ops.check_sampling_args(temperature, top_p, top_k, seed)
+    n_prompts = len(input_ids)
+    (ds, seq), (ts, seq_t), (ps, seq_p), (ks, seq_k), (mps, seq_m) = (_per_prompt(name, v, n_prompts) for name, v in (
+        ("do_sample", do_sample), ("temperature", temperature), ("top_p", top_p), ("top_k", top_k), ("min_p", min_p)))
+    for d in ds:
+        if not isinstance(d, bool):
+            raise TypeError(f"do_sample must be a bool or one bool per prompt, got {do_sample!r}")
+    if not isinstance(return_logprobs, bool):
+        raise TypeError(f"return_logprobs must be a bool, got {return_logprobs!r}")
+    for b in range(n_prompts):                   # (a greedy prompt's sampling parameters are not looked at, as before)
+        if ds[b]:
+            ops.check_sampling_args(ts[b], ps[b], ks[b], seed)
+            ops.check_row_sampling_args(min_p=mps[b])
+    per_row = seq or seq_t or seq_p or seq_k or seq_m or return_logprobs or any(d and m != 0 for d, m in zip(ds, mps))
+    if per_row:
+        for b in range(n_prompts):
+            if ds[b]:
+                ops.check_row_sampling_args(ts[b], ps[b], ks[b], mps[b])
+        ops._int_in("seed", seed, 0, 2 ** 64)
     penalize = ops.check_repetition_penalty(repetition_penalty) != 1.0
     eos = set() if eos_token_id is None else ({int(eos_token_id)} if isinstance(eos_token_id, int) else {int(e) for e in eos_token_id})
     lm = model.model.language_model
     # the token sets of the penalty: every prompt id as passed (range-checked on the host before any device work)
     sets = ops.token_sets(input_ids, model.lm_head.out_features, model.lm_head.weight.device) if penalize else None
-    select = _selector(do_sample, temperature, top_p, top_k, seed, repetition_penalty, sets)
+    rows = None
+    if per_row:
+        # one device array per parameter, built once per call; a greedy prompt is a temperature-0 row with every filter off
+        dev0 = model.lm_head.weight.device
+        rows = dict(temperature=_h2d([float(t) if d else 0.0 for d, t in zip(ds, ts)], torch.float32, dev0),
+                    top_p=_h2d([float(x) if d else 1.0 for d, x in zip(ds, ps)], torch.float32, dev0),
+                    top_k=_h2d([k if d else 0 for d, k in zip(ds, ks)], torch.int32, dev0),
+                    min_p=_h2d([float(x) if d else 0.0 for d, x in zip(ds, mps)], torch.float32, dev0))
+    select = _selector(do_sample, temperature, top_p, top_k, seed, repetition_penalty, sets, rows, return_logprobs)
     register_paged_attention()
     p = _packed_inputs(model, input_ids, pixel_values, image_grid_thw, images_per_prompt, budgets)
     lengths = p["lengths"]
@@ -404,12 +473,12 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
         lm.config._attn_implementation = ATTN_NAME_PAGED
         first_logits, step_pos = _prefill(model, lm, state, p, bt)
         seqlens = _h2d(lengths, torch.int32, dev)
-        row_ids = torch.arange(n, dtype=torch.int64, device=dev) if do_sample or penalize else None
+        row_ids = torch.arange(n, dtype=torch.int64, device=dev) if per_row or do_sample or penalize else None
         if graphs is not None:
-            tokens, step_logits = _graph_decode(model, lm, graphs, first_logits, step_pos, seqlens, bt, max_new_tokens, lookahead, eos, select,
+            tokens, step_logits, logprobs = _graph_decode(model, lm, graphs, first_logits, step_pos, seqlens, bt, max_new_tokens, lookahead, eos, select,
                                                 row_ids, return_logits)
         else:
-            tokens, step_logits = _eager_decode(model, lm, state, pages, lengths, first_logits, step_pos, seqlens, bt, max_new_tokens, eos,
+            tokens, step_logits, logprobs = _eager_decode(model, lm, state, pages, lengths, first_logits, step_pos, seqlens, bt, max_new_tokens, eos,
                                                 select, row_ids, return_logits)
     finally:
         lm.config._attn_implementation = old_impl
@@ -418,6 +487,8 @@ def packed_generate(model, input_ids: Sequence[torch.Tensor], pixel_values: torc
     out = {"tokens": tokens, "kept": p["kept"], "first_logits": first_logits, "pool": pool}
     if return_logits:
         out["logits"] = step_logits
+    if return_logprobs:
+        out["logprobs"] = logprobs
     return out
 
 

@@ -975,6 +975,60 @@ def sample_tokens(logits: torch.Tensor, temperature: float, top_p: float = 1.0, 
     return (tokens, kept) if return_kept else tokens
 
 
+def check_row_sampling_args(temperature=1.0, top_p=1.0, top_k=0, min_p=0.0) -> Tuple[float, float, int, float]:
+    """Host checks of one row's parameters for vsel_sample_tokens_rows: check_sampling_args' rules with temperature 0 allowed (a greedy
+    row), top_k below 2^31 (int32 on the device) and min_p in [0, 1].  -> the values as the float32 / int32 the device arrays hold."""
+    t, p, mp = C.c_float(float(temperature)).value, C.c_float(float(top_p)).value, C.c_float(float(min_p)).value
+    if not (math.isfinite(t) and t >= 0):
+        raise ValueError(f"temperature must be finite and >= 0 (as float32; 0: greedy), got {temperature!r}")
+    if not (0.0 < float(top_p) <= 1.0 and p > 0):
+        raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+    if not 0.0 <= float(min_p) <= 1.0:
+        raise ValueError(f"min_p must be in [0, 1], got {min_p!r}")
+    return t, p, _int_in("top_k", top_k, 0, 2 ** 31), mp
+
+
+def sample_tokens_rows(logits: torch.Tensor, temperature=None, top_p=None, top_k=None, min_p=None, seed: int = 0,
+                       row_ids: Optional[torch.Tensor] = None, step: int = 0, return_kept: bool = False, return_logprobs: bool = False):
+    """vsel_sample_tokens_rows: sample_tokens with each row's own parameters ("per-row parameters").  temperature, top_p,
+    min_p: None (off: 1, 1, 0), a Python number for every row, or a float32 tensor [B] on logits' device; top_k likewise with int32.
+    temperature 0 makes a row greedy (argmax, lowest index among equal values; its other parameters are ignored); min_p is HF's
+    MinPLogitsWarper, applied after top-k and top-p.  Numbers are range-checked here; tensors are checked for dtype, shape and device only,
+    and a row whose values are out of range gives token -1, kept 0 and logprob NaN, like a row with invalid logits.  No host
+    synchronisation.  -> int64 [B] tokens; with return_kept also int32 [B], the size of each row's final set; with return_logprobs also
+    float32 [B], the log-probability of each token under the distribution it was drawn from (greedy rows: the log-softmax of the logits)."""
+    scalars = {n: v for n, v in (("temperature", temperature), ("top_p", top_p), ("top_k", top_k), ("min_p", min_p))
+               if v is not None and not isinstance(v, torch.Tensor)}
+    t, p, k, mp = check_row_sampling_args(**scalars)
+    host = dict(temperature=t, top_p=p, top_k=k, min_p=mp)
+    _int_in("seed", seed, 0, 2 ** 64)
+    _int_in("step", step, 0, 2 ** 64)
+    code, b, v, stride = _logit_rows(logits)
+    arrays = {}
+    for name, val in (("temperature", temperature), ("top_p", top_p), ("top_k", top_k), ("min_p", min_p)):
+        dt = torch.int32 if name == "top_k" else torch.float32
+        if isinstance(val, torch.Tensor):
+            if val.dtype != dt or val.shape != (b,):
+                raise TypeError(f"{name} must be a number or a {str(dt)[6:]} tensor [{b}], got {val.dtype} {tuple(val.shape)}")
+            arrays[name] = val
+    if row_ids is not None and (row_ids.dtype != torch.int64 or row_ids.shape != (b,)):
+        raise TypeError(f"row_ids must be int64 [{b}]")
+    dev = _dev(logits, row_ids, *arrays.values(), strided_ok=True)
+    for name in scalars:
+        arrays[name] = torch.full((b,), host[name], dtype=torch.int32 if name == "top_k" else torch.float32, device=dev)
+    arrays = {name: a.contiguous() for name, a in arrays.items()}
+    ptr = {name: _p(arrays.get(name)) for name in ("temperature", "top_p", "top_k", "min_p")}
+    if row_ids is not None:
+        row_ids = row_ids.contiguous()
+    tokens = torch.empty(b, dtype=torch.int64, device=dev)
+    kept = torch.empty(b, dtype=torch.int32, device=dev) if return_kept else None
+    logprobs = torch.empty(b, dtype=torch.float32, device=dev) if return_logprobs else None
+    N.check(N.lib().vsel_sample_tokens_rows(_stream(), logits.data_ptr(), code, b, v, stride, ptr["temperature"], ptr["top_p"], ptr["top_k"],
+                                            ptr["min_p"], seed, _p(row_ids), step, tokens.data_ptr(), _p(kept), _p(logprobs)))
+    out = (tokens,) + ((kept,) if return_kept else ()) + ((logprobs,) if return_logprobs else ())
+    return out if len(out) > 1 else tokens
+
+
 def check_repetition_penalty(penalty) -> float:
     """Host check of a repetition penalty as HF's RepetitionPenaltyLogitsProcessor takes it: a number > 0, here also finite (and > 0 as
     the float32 the library computes with).  -> float(penalty)."""
@@ -1147,6 +1201,6 @@ def token_logprobs(logits: torch.Tensor, targets: torch.Tensor, ignore_index: in
 for _name in ("token_logprob_fwd", "token_logprob_bwd", "token_logprobs","lis_scores", "lis_select", "lis_select_permuted", "gelu_colsum", "colsum_linear", "lis_select_presummed", "lis_select_varlen",
               "hard_topk", "gather_rows", "soft_topk_fwd", "soft_topk_bwd", "lis_train_fwd", "lis_train_bwd", "lis_train_bwd_factors", "factors_to_grads", "lis_scores_bwd",
               "splice", "splice_batched", "lis_select_splice", "topk_select_splice", "varlen_attn", "varlen_attn_fwd_lse", "varlen_attn_bwd", "varlen_attn_kv",
-              "attn_head_major", "paged_attn", "kvcache_attn", "sample_tokens", "token_sets", "repetition_penalty", "decode_advance"):
+              "attn_head_major", "paged_attn", "kvcache_attn", "sample_tokens", "sample_tokens_rows", "token_sets", "repetition_penalty", "decode_advance"):
     globals()[_name] = _device_guard(globals()[_name])
 del _name
