@@ -82,7 +82,11 @@ typedef enum vsel_debug_knob {
   VSEL_KNOB_TRAIN_FUSED = 22,     /* 0 / 1: training backward of one row of <= 4096 scores (bf16 weights) in five launches -- the soft top-k backward in the
                                      prologue of the weighted column sums, both projections in one launch, one finish kernel, both rank-1 writes in one
                                      launch -- instead of ten (default 1; env VSEL_TRAIN_FUSED); bit-identical */
-  VSEL_KNOB_COUNT = 23
+  VSEL_KNOB_LIS_PROJ_SUM = 23,    /* bf16x3 projections of the scorer: 0 = slab GEMM + finish kernel twice (four launches, split-K slabs in memory), 1 = the
+                                     K-slices of an output tile summed in LDS by the workgroup that owns it, finish arithmetic in its epilogue (two
+                                     launches, no slabs) whenever both projections have <= 16 K-slices, -1 (default) by segment count;
+                                     env VSEL_PROJ_SUM; bit-identical */
+  VSEL_KNOB_COUNT = 24
 } vsel_debug_knob;
 
 /* Set knob to value (clamped to the knob's range).  *previous (may be NULL) receives the value it had.

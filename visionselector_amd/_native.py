@@ -95,7 +95,7 @@ DEBUG_SIGNATURES = {
 KNOBS = {"lis_small_path": 0, "lis_fused_select": 1, "attn_waves": 2, "attn_pack": 3, "attn_split": 4, "attn_split_q64": 5, "attn_bwd_split": 6,
          "lis_splice_fused": 7, "attn_bwd_waves": 8, "attn_tail_first": 9, "lis_seg_sums": 10, "attn_xcd_queue": 11, "attn_rows64": 12,
          "attn_bwd_dq64": 13, "attn_bwd_dkdv64": 14, "attn_static": 15, "attn_skip_empty": 16, "attn_gqa": 17, "attn_gqa_form": 18,
-         "attn_bwd_updown": 19, "attn_key_parts": 20, "lis_gather": 21, "train_fused": 22}
+         "attn_bwd_updown": 19, "attn_key_parts": 20, "lis_gather": 21, "train_fused": 22, "lis_proj_sum": 23}
 
 _lib = None
 

@@ -110,7 +110,10 @@ ASM_READ_KERNELS = (("attn.hip", "varlen_attn_fwd_kernelI"), ("attn_bwd.hip", "a
                     # the generated one-statement bodies clobber v32-255 / a0-255 / s40-99: everything the C++ around them keeps live must
                     # fit in what is left, without scratch
                     ("attn_fwd64.hip", "attn_fwd64_kernel"), ("attn_fwd_gqa64.hip", "attn_fwd_gqa64_kernel"), ("attn_bwd_dq64.hip", "attn_bwd_dq64_kernel"),
-                    ("attn_bwd_dkdv64.hip", "attn_bwd_dkdv64_kernel"), ("attn_fwd64_parts.hip", "attn_fwd64_parts_kernel"))
+                    ("attn_bwd_dkdv64.hip", "attn_bwd_dkdv64_kernel"), ("attn_fwd64_parts.hip", "attn_fwd64_parts_kernel"),
+                    # no asm reads, but 16-wave workgroups: 128 registers per wave is the whole budget (csrc/proj_bf16x3.h), and scratch
+                    # in these two latency-bound kernels is a defect
+                    ("lis.hip", "gemm_nt_sum_bf16x3_kernel"), ("lis.hip", "gemm_nn_sum_bf16x3_kernel"))
 
 
 def extra_flags() -> list:

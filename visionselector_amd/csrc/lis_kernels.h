@@ -1011,6 +1011,21 @@ inline int run_colsum(hipStream_t st, const T* h, const vsel_segments* seg, int 
                           seg_sums_form(p, seg), p.mfma_bf16 ? (uint16_t*)(ws + p.off_xs) : nullptr);
 }
 
+// The bf16x3 projections with their split-K slices summed in LDS (gemm_nt_sum / gemm_nn_sum_bf16x3_kernel: two launches, no slabs)
+// instead of slab GEMM + finish kernel twice (four launches): knob LIS_PROJ_SUM 0 never, 1 whenever both projections have at most
+// kSumMaxSlices K-slices (one wave per slice in one workgroup), -1 (default) from kProjSumMinSeg segments.  Same bits either way.
+// Measured (tools/ab_proj.py, profiles/proj_sum_ab.txt; us of the four / two projection launches, forms alternated, 7B geometry): 8 images
+// 34.7 / 30.6 with the step 83-90 / 85, 16 images 37.0 / 41.2, 32 images 38.6 / 41.2 (one m-tile: one workgroup per 32 weight rows leaves
+// most CUs idle, the slab form's 14 slices on 14 CUs win), 64 images 43.6 / 35.7 (step 431-448 / 428-429), 128 images 55.1 / 36.9
+// (step 855-857 / 812-844), 3B x 512 60.1 / 43.0, LLaVA-OV x 48 (16 slices) 47.4 / 36.7: a gain from two m-tiles on, and 48 segments is
+// the smallest count at which one was measured.
+constexpr int kProjSumMinSeg = 48;
+inline bool proj_sum_form(const LisPlan& p) {
+  const int f = knob(VSEL_KNOB_LIS_PROJ_SUM);
+  if (f == 0 || p.ks1 > kSumMaxSlices || p.ks2 > kSumMaxSlices || p.d * p.hd >= (1ll << 30)) return false;      // (32-bit weight offsets)
+  return f > 0 || (p.S > 8 && p.S >= kProjSumMinSeg);
+}
+
 // stage 2: partials -> xbar -> kbar -> (w, c)   (small, latency-bound kernels)
 // col_sums (optional): [S, D] fp32 column sums of the tokens supplied by the producer (vsel_lis_select_presummed); they take
 // the place of the sweep-1 partials as a single "chunk", everything downstream is unchanged.
@@ -1041,6 +1056,17 @@ inline int run_proj(hipStream_t st, const vsel_segments* seg, const vsel_scorer*
       }
       const unsigned mtiles = (unsigned)cdiv(S, 32);
       const int m_pad = 32 * (int)mtiles;
+      if (proj_sum_form(p)) {
+        // split-K summed in LDS (proj_bf16x3.h): the two finish launches and both slabs are gone, same bits
+        VSEL_LAUNCH(gemm_nt_sum_bf16x3_kernel, dim3((unsigned)cdiv(hd, 32), mtiles), dim3(64 * p.ks1), 0, st, xs, (const uint16_t*)sc->wk,
+                           S, hd, d, p.kslice1, p.ks1, (int)mtiles, (const uint16_t*)sc->bk, (const uint16_t*)sc->bq, kbar, ksp, cpart,
+                           p.n_cpart);
+        VSEL_AFTER_LAUNCH(st, "gemm_nt_bf16x3_kernel");
+        VSEL_LAUNCH(gemm_nn_sum_bf16x3_kernel, dim3((unsigned)cdiv(d, 64), mtiles), dim3(64 * p.ks2), 0, st, ksp, (const uint16_t*)sc->wq,
+                           S, d, hd, p.kslice2, p.ks2, (int)mtiles, cpart, p.n_cpart, w, c);
+        VSEL_AFTER_LAUNCH(st, "gemm_nn_bf16x3_kernel");
+        return VSEL_OK;
+      }
       VSEL_LAUNCH(gemm_nt_bf16x3_kernel<kProjWaves>, dim3((unsigned)cdiv(hd, 64), (unsigned)cdiv(mtiles, kProjWaves), p.ks1), dim3(64 * kProjWaves), 0, st, xs,
                          (const uint16_t*)sc->wk, S, hd, d, p.kslice1, part1, (int)mtiles);
       VSEL_AFTER_LAUNCH(st, "gemm_nt_bf16x3_kernel");

@@ -283,4 +283,227 @@ static __attribute__((unused)) __global__ __launch_bounds__(256) void w_finish_k
   }
 }
 
+// =====================================================================================================================
+// Split-K summed in LDS: one workgroup owns an output tile and ALL its K-slices (one wave per slice), deposits every slice's
+// fp32 tile in LDS and, behind one __syncthreads(), adds them in slice order exactly as strided_sum adds the slabs
+// (acc = 0; acc += slice 0; acc += slice 1; ...), then runs the finish kernel's arithmetic itself.  No slabs in memory, no finish
+// launches, no hand-off between workgroups.  Every slice starts from a zero accumulator and runs the k-steps, operand layout
+// and MFMA order (b3, b2, b1) of the slab kernels above, so each output element is the slab path's bit for bit (an MFMA output
+// element depends on its own operand row and column only, not on where in the tile it sits).
+// Registers: up to 16 waves = 4 per SIMD, 128 registers each -- hence smaller tiles per wave than the slab kernels.
+constexpr int kSumMaxSlices = 16;      // waves per workgroup (1024 threads); a projection with more K-slices keeps the slab form
+
+// sum_{s<n} p[s * stride] of LDS in index order, as strided_sum: every read in flight at once (clamped index), plain adds in order
+__device__ __forceinline__ float slice_sum(const float* p, int n, int stride) {
+  float v[kSumMaxSlices];
+#pragma unroll
+  for (int u = 0; u < kSumMaxSlices; ++u) v[u] = p[min(u, n - 1) * stride];
+  float acc = 0.f;
+#pragma unroll
+  for (int u = 0; u < kSumMaxSlices; ++u)
+    if (u < n) acc += v[u];
+  return acc;
+}
+
+// NT: kbar = xbar Wk^T + bk, with kbar_finish_split_kernel's outputs (fp32 kbar, fragment-major planes, cpart).
+// grid (ceil(N/32), m_tiles), block 64 * KS: wave ks owns k-slice ks of a 32 (n) x 32 (m) tile.  Requires K % 16 == 0.
+// (One weight tile per wave, not the slab kernel's two: a lane's 16-byte weight load touches a cache line of its own, 64 lines per
+// instruction, and a workgroup issues those for all K; with 64-row tiles -- half the workgroups, half the plane reads -- the kernel
+// took 27 us instead of 18 at 128 images, profiles/proj_sum_ab.txt.)
+static __attribute__((unused)) __global__ __launch_bounds__(64 * kSumMaxSlices) void gemm_nt_sum_bf16x3_kernel(
+    const uint16_t* __restrict__ xs, const uint16_t* __restrict__ w, int M, int N, int K, int kslice, int KS, int m_tiles,
+    const uint16_t* __restrict__ bk, const uint16_t* __restrict__ bq, float* __restrict__ kbar, uint16_t* __restrict__ ksp,
+    float* __restrict__ cpart, int n_cpart) {
+  __shared__ float slab[kSumMaxSlices][32][32];     // [slice][n][m]: an MFMA C row (32 lanes = 32 m) is one conflict-free store
+  __shared__ float red[32][33];
+  const int lane = threadIdx.x & 63;
+  const int i = lane & 31, kg = lane >> 5;
+  const int mt = blockIdx.y, ksteps = K >> 4;
+  const int n0 = blockIdx.x * 32;
+  const int ks = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (wave-uniform: slice bounds and bases stay in SGPRs)
+  {
+    const int k_begin = ks * kslice;
+    const int k_end = min(K, k_begin + kslice);
+    // per-lane 32-bit element offsets on wave-uniform bases (the host checks N * K < 2^30): registers go to loads in flight, not addresses
+    const uint32_t wo0 = (uint32_t)min(n0 + i, N - 1) * (uint32_t)K + 8 * kg;
+    const uint32_t xo_l = lane * 8;
+    const int64_t plane = (int64_t)m_tiles * ksteps * 512;          // elements per plane
+    const uint16_t* xb = xs + (int64_t)mt * ksteps * 512;
+    f32x16 acc0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc0[r] = 0.f;
+    int k0 = k_begin;
+    constexpr int KB = 4;      // 64 load registers + 16 accumulators
+    for (; k0 + 16 * KB <= k_end; k0 += 16 * KB) {
+      u32x4 a0[KB], b1[KB], b2[KB], b3[KB];
+      const uint16_t* wk0 = w + k0;
+      const uint16_t* xk = xb + (int64_t)(k0 >> 4) * 512;
+#pragma unroll
+      for (int u = 0; u < KB; ++u) {
+        a0[u] = *reinterpret_cast<const u32x4*>(wk0 + 16 * u + wo0);
+        b1[u] = *reinterpret_cast<const u32x4*>(xk + 512 * u + xo_l);
+        b2[u] = *reinterpret_cast<const u32x4*>(xk + plane + 512 * u + xo_l);
+        b3[u] = *reinterpret_cast<const u32x4*>(xk + 2 * plane + 512 * u + xo_l);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < KB; ++u) {
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a0[u]), as_bf16x8(b3[u]), acc0, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a0[u]), as_bf16x8(b2[u]), acc0, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a0[u]), as_bf16x8(b1[u]), acc0, 0, 0, 0);
+      }
+    }
+    for (; k0 < k_end; k0 += 16) {
+      const uint16_t* xk = xb + (int64_t)(k0 >> 4) * 512;
+      const u32x4 a0 = *reinterpret_cast<const u32x4*>(w + k0 + wo0);
+      const u32x4 b1 = *reinterpret_cast<const u32x4*>(xk + xo_l);
+      const u32x4 b2 = *reinterpret_cast<const u32x4*>(xk + plane + xo_l);
+      const u32x4 b3 = *reinterpret_cast<const u32x4*>(xk + 2 * plane + xo_l);
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a0), as_bf16x8(b3), acc0, 0, 0, 0);
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a0), as_bf16x8(b2), acc0, 0, 0, 0);
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a0), as_bf16x8(b1), acc0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = (r & 3) + 8 * (r >> 2) + 4 * kg;
+      slab[ks][row][i] = acc0[r];
+    }
+  }
+  __syncthreads();
+  // kbar_finish_split_kernel's arithmetic on the tile's elements; thread -> (n = e >> 5, m = e & 31)
+  const int nthr = blockDim.x;
+  const int m = 32 * mt + i;
+  for (int e = threadIdx.x; e < 32 * 32; e += nthr) {
+    const int nl = e >> 5, n = n0 + nl;
+    float cterm = 0.f;
+    if (m < M && n < N) {
+      float v = slice_sum(&slab[0][nl][i], KS, 32 * 32);
+      v += bf16_to_f32(bk[n]);
+      kbar[(int64_t)m * N + n] = v;
+      uint32_t b1, b2, b3;
+      split3(v, b1, b2, b3);
+      const int nks = N >> 4;
+      ksp[frag_off(0, m, n, m_tiles, nks)] = (uint16_t)b1;
+      ksp[frag_off(1, m, n, m_tiles, nks)] = (uint16_t)b2;
+      ksp[frag_off(2, m, n, m_tiles, nks)] = (uint16_t)b3;
+      cterm = bf16_to_f32(bq[n]) * v;
+    }
+    red[nl][i] = cterm;
+  }
+  __syncthreads();
+  // cpart[m][n / 8]: the 8 consecutive h of a group in order, from 0.f
+  for (int q = threadIdx.x; q < 4 * 32; q += nthr) {
+    const int g = q >> 5, by = (n0 >> 3) + g;
+    if (m < M && by < n_cpart) {
+      float t = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) t += red[8 * g + j][i];
+      cpart[(int64_t)m * n_cpart + by] = t;
+    }
+  }
+}
+
+// NN: w = kbar Wq, with w_finish_kernel's outputs (w [M, N] row-major and, from the workgroups of the first column strip, c).
+// grid (ceil(N/64), m_tiles), block 64 * KS: wave ks owns k-slice ks of a 64 (n) x 32 (m) tile.  Lane (i, kg) owns 2 consecutive n
+// (n0 + 2i, + 1) and k rows k0 + 8kg .. +7: eight 4-byte row loads (a wave reads one whole 128-byte line per weight row), then the
+// register transpose of gemm_nn_bf16x3_kernel builds the A fragments of the two 32x32 tiles "n = n0 + 2 i' + t": 32 accumulator
+// registers instead of 128, so 4 k-steps of loads fit beside them.  The tile is deposited [slice][n][m] and stored as 256-byte
+// pieces of w's rows.  Requires K % 16 == 0 and N % 8 == 0.
+static __attribute__((unused)) __global__ __launch_bounds__(64 * kSumMaxSlices) void gemm_nn_sum_bf16x3_kernel(
+    const uint16_t* __restrict__ xs, const uint16_t* __restrict__ w, int M, int N, int K, int kslice, int KS, int m_tiles,
+    const float* __restrict__ cpart, int n_cpart, float* __restrict__ wout, float* __restrict__ c) {
+  __shared__ float slab[kSumMaxSlices][64][33];     // (33: the epilogue reads with n across the lanes)
+  __shared__ float red[8][33];
+  const int lane = threadIdx.x & 63;
+  const int i = lane & 31, kg = lane >> 5;
+  const int mt = blockIdx.y, ksteps = K >> 4;
+  const int n0 = blockIdx.x * 64;
+  const int ks = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nthr = blockDim.x;
+  {
+    const int k_begin = ks * kslice;
+    const int k_end = min(K, k_begin + kslice);
+    // per-lane 32-bit element offsets on wave-uniform bases (the host checks N * K < 2^30)
+    const uint32_t wo = (uint32_t)(8 * kg) * (uint32_t)N + (uint32_t)min(n0 + 2 * i, N - 2);
+    const uint32_t xo_l = lane * 8;
+    const int64_t plane = (int64_t)m_tiles * ksteps * 512;
+    const uint16_t* xb = xs + (int64_t)mt * ksteps * 512;
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    auto step = [&](const uint32_t (&wv)[8], u32x4 b1, u32x4 b2, u32x4 b3) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        // element t of row e sits in half t of its dword; pack (e even -> low half, e odd -> high half)
+        const uint32_t sel = t ? 0x07060302u : 0x05040100u;
+        u32x4 a;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[q] = __builtin_amdgcn_perm(wv[2 * q + 1], wv[2 * q], sel);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a), as_bf16x8(b3), acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a), as_bf16x8(b2), acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a), as_bf16x8(b1), acc[t], 0, 0, 0);
+      }
+    };
+    constexpr int KB = 4;      // 4 x 20 load registers + 32 accumulators
+    int k0 = k_begin;
+    for (; k0 + 16 * KB <= k_end; k0 += 16 * KB) {
+      uint32_t wv[KB][8];
+      u32x4 b1[KB], b2[KB], b3[KB];
+      const uint16_t* xk = xb + (int64_t)(k0 >> 4) * 512;
+#pragma unroll
+      for (int u = 0; u < KB; ++u) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) wv[u][e] = *reinterpret_cast<const uint32_t*>(w + (int64_t)(k0 + 16 * u + e) * N + wo);
+        b1[u] = *reinterpret_cast<const u32x4*>(xk + 512 * u + xo_l);
+        b2[u] = *reinterpret_cast<const u32x4*>(xk + plane + 512 * u + xo_l);
+        b3[u] = *reinterpret_cast<const u32x4*>(xk + 2 * plane + 512 * u + xo_l);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < KB; ++u) step(wv[u], b1[u], b2[u], b3[u]);
+    }
+    for (; k0 < k_end; k0 += 16) {
+      uint32_t wv[8];
+      const uint16_t* xk = xb + (int64_t)(k0 >> 4) * 512;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) wv[e] = *reinterpret_cast<const uint32_t*>(w + (int64_t)(k0 + e) * N + wo);
+      step(wv, *reinterpret_cast<const u32x4*>(xk + xo_l), *reinterpret_cast<const u32x4*>(xk + plane + xo_l),
+           *reinterpret_cast<const u32x4*>(xk + 2 * plane + xo_l));
+    }
+    // acc[t][r] = C[n = n0 + 2*irow + t][m = 32*mt + i], irow = (r&3) + 8*(r>>2) + 4*kg
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int irow = (r & 3) + 8 * (r >> 2) + 4 * kg;
+      slab[ks][2 * irow][i] = acc[0][r];
+      slab[ks][2 * irow + 1][i] = acc[1][r];
+    }
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < 64 * 32; e += nthr) {
+    const int cl = e & 63, ml = e >> 6;
+    const int n = n0 + cl, m = 32 * mt + ml;
+    if (m < M && n < N) {
+      float v = 0.f;
+      for (int s = 0; s < KS; ++s) v += slab[s][cl][ml];
+      wout[(int64_t)m * N + n] = v;
+    }
+  }
+  if (blockIdx.x == 0) {
+    // c[m] as w_finish_kernel: thread (m, nj) sums cpart[m][nj], [nj + 8], ... then the 8 partials are added in fixed order
+    for (int q = threadIdx.x; q < 8 * 32; q += nthr) {
+      const int nj = q >> 5, m = 32 * mt + (q & 31);
+      red[nj][q & 31] = (m < M && nj < n_cpart) ? strided_sum(cpart + (int64_t)m * n_cpart + nj, (n_cpart - nj + 7) / 8, 8) : 0.f;
+    }
+    __syncthreads();
+    if (threadIdx.x < 32 && 32 * mt + (int)threadIdx.x < M) {
+      float t = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) t += red[j][threadIdx.x];
+      c[32 * mt + threadIdx.x] = t;
+    }
+  }
+}
+
 }  // namespace vsel
