@@ -311,6 +311,14 @@ def test_errors_are_loud(ops):
         ops.lis_select(h.half(), wq, bq, wk, bk, 2)
     with pytest.raises(ValueError):
         ops.lis_select(h[:, :32].contiguous(), wq, bq, wk, bk, 2)
+    # tokens narrower than the scorer's in_features: the library reads rows of the scorer's width, so every select entry refuses
+    # them before any launch
+    narrow = h[:, :32].contiguous()
+    perm = torch.randperm(16).cuda()
+    with pytest.raises(ValueError, match="token width 32 != scorer in_features 64"):
+        ops.lis_select_permuted(narrow, perm, torch.argsort(perm), wq, bq, wk, bk, 2)
+    with pytest.raises(ValueError, match="token width 32 != scorer in_features 64"):
+        ops.lis_select_presummed(narrow, narrow.float().sum(0, keepdim=True), wq, bq, wk, bk, 2)
 
 
 # ---------------------------------------------------------------------------------------------------

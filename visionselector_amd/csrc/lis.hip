@@ -10,12 +10,6 @@ int check_segments(const vsel_segments* seg, bool need_k) { return check_segment
 
 using namespace vsel;
 
-// small-batch form (lis_small.h): used up to small_path_max_seg() segments per call.  Measured on MI355X (Qwen2.5-VL-7B geometry,
-// us per call, small form vs batched form): 1 image 36.2 vs 51.7, 2 images 43.8 vs 55.8, 3 images 52.2 vs 60.8, 4 images 60.4 vs
-// 65.3, 8 images 102.3 vs 86.2 -- the redundant prologues grow with the segment count, so the default limit is 4.
-// VSEL_SMALL_PATH=<n> / knob VSEL_KNOB_LIS_SMALL_PATH set the limit (0 = never; at most kSmallMaxSeg).
-static_assert(kSmallMaxSeg == 8, "common.hip clamps VSEL_KNOB_LIS_SMALL_PATH to 8");
-static inline int small_path_max_seg() { return knob(VSEL_KNOB_LIS_SMALL_PATH); }
 #ifdef VSEL_TRACE
 // copies the stamps of the last small-batch call: out[kTraceKernels][kTraceBlocks][kTraceSlots] (tools/trace_small.py)
 extern "C" int vsel_debug_read_trace(unsigned long long* out, int clear) {
@@ -35,43 +29,43 @@ extern "C" int vsel_debug_read_trace(unsigned long long* out, int clear) {
 // 428.7 -> up to 48.  VSEL_FUSED_SELECT=<n> / knob VSEL_KNOB_LIS_FUSED_SELECT.
 static inline int fused_select_max_seg() { return knob(VSEL_KNOB_LIS_FUSED_SELECT); }
 
-static bool use_small_path(const vsel_segments* seg, const vsel_scorer* sc, const LisPlan& p) {
-  return seg->n_seg <= small_path_max_seg() && small_path_ok(seg, sc, p);
+int vsel::lis_scores_stage(hipStream_t st, const void* h, vsel_dtype hdtype, const vsel_segments* seg, const vsel_scorer* sc, char* ws,
+                           const LisPlan& p, float* scores, const int64_t* out_map, const float* col_sums, bool small) {
+  return with_dtypes(hdtype, sc->wdtype, [&](auto t, auto tw) {
+    using T = decltype(t);
+    const T* hp = (const T*)h;
+    int rc;
+    if (!col_sums && (rc = run_colsum<T>(st, hp, seg, (int)sc->d, ws, p))) return rc;
+    if (small) {
+      // a handful of segments (lis_small.h): two projection launches instead of up to five, bit-identical results
+      if ((rc = run_proj_small(st, seg, sc, ws, p, col_sums))) return rc;
+      return run_score_small<T>(st, hp, seg, sc, ws, p, scores, out_map);
+    }
+    if ((rc = run_proj<decltype(tw)>(st, seg, sc, ws, p, col_sums))) return rc;
+    return run_score<T>(st, hp, seg, sc, ws, p, scores, out_map);
+  });
 }
 
-// Calls f(T{}, TW{}) with T the element type of the tokens (hdtype) and TW that of the scorer weights (wdtype): bf16_t or float.
-// Both dtypes have passed check_scorer.
-template <typename F>
-static int with_dtypes(vsel_dtype hdtype, vsel_dtype wdtype, F&& f) {
-  if (hdtype == VSEL_BF16) return wdtype == VSEL_BF16 ? f(bf16_t{}, bf16_t{}) : f(bf16_t{}, float{});
-  return wdtype == VSEL_BF16 ? f(float{}, bf16_t{}) : f(float{}, float{});
-}
-
-template <typename T, typename TW>
-static int lis_select_impl(hipStream_t st, const T* h, const vsel_segments* seg, const vsel_scorer* sc, char* ws, const LisPlan& p,
-                           T* out, int64_t* idx, float* scores, const int64_t* l2p = nullptr, const int64_t* p2l = nullptr,
-                           const float* col_sums = nullptr) {
-  int rc = VSEL_OK;
-  if (!col_sums) rc = run_colsum<T>(st, h, seg, (int)sc->d, ws, p);
+// scores -> hard top-k -> kept rows; l2p / p2l (both or neither) and col_sums are optional
+static int lis_select_impl(void* stream, const void* h, vsel_dtype hdtype, const vsel_segments* seg, const vsel_scorer* sc, void* ws,
+                           const LisPlan& p, void* out, int64_t* idx, float* scores, const int64_t* l2p = nullptr,
+                           const int64_t* p2l = nullptr, const float* col_sums = nullptr) {
+  hipStream_t st = (hipStream_t)stream;
+  VSEL_PROF_BEGIN(st);
+  const bool small = use_small_path(seg, sc, p);
+  int rc = lis_scores_stage(st, h, hdtype, seg, sc, (char*)ws, p, scores, p2l, col_sums, small);
   if (rc) return rc;
-  if (use_small_path(seg, sc, p)) {
-    // a handful of segments: five launches instead of nine, bit-identical results (lis_small.h)
-    if ((rc = run_proj_small(st, seg, sc, ws, p, col_sums))) return rc;
-    if ((rc = run_score_small<T>(st, h, seg, sc, ws, p, scores, p2l))) return rc;
-    return launch_select_gather_small<T>(st, h, (int)sc->d, seg, scores, idx, out, l2p);
-  }
-  rc = run_proj<TW>(st, seg, sc, ws, p, col_sums);
-  if (rc) return rc;
-  rc = run_score<T>(st, h, seg, sc, ws, p, scores, p2l);
-  if (rc) return rc;
-  // up to fused_select_max_seg() segments: the radix select runs inside every gather workgroup (one launch less; same indices)
-  // (every gather workgroup repeats its segment's select: not when there are thousands of them -- 32 images at 50 % retain:
-  // 308.0 vs 305.7 us)
-  if (seg->n_seg <= fused_select_max_seg() && seg->n_seg * cdiv(seg->k, 16) <= 1536)
-    return launch_select_gather_small<T>(st, h, (int)sc->d, seg, scores, idx, out, l2p);
-  rc = launch_select(st, scores, seg, idx, nullptr);
-  if (rc) return rc;
-  return launch_gather<T>(st, h, (int)sc->d, seg, idx, out, l2p);
+  return with_dtype(hdtype, [&](auto t) {
+    using T = decltype(t);
+    // up to fused_select_max_seg() segments: the radix select runs inside every gather workgroup (one launch less; same indices)
+    // (every gather workgroup repeats its segment's select: not when there are thousands of them -- 32 images at 50 % retain:
+    // 308.0 vs 305.7 us); the small-batch form always selects there
+    if (small || (seg->n_seg <= fused_select_max_seg() && seg->n_seg * cdiv(seg->k, 16) <= 1536))
+      return launch_select_gather_small<T>(st, (const T*)h, (int)sc->d, seg, scores, idx, (T*)out, l2p);
+    int rc2 = launch_select(st, scores, seg, idx, nullptr);
+    if (rc2) return rc2;
+    return launch_gather<T>(st, (const T*)h, (int)sc->d, seg, idx, (T*)out, l2p);
+  });
 }
 
 extern "C" size_t vsel_lis_workspace_bytes(const vsel_segments* seg, int64_t d, int64_t hd) {
@@ -84,14 +78,10 @@ static int lis_common_checks(const void* h, const vsel_segments* seg, const vsel
   if (!h) return fail(VSEL_ERR_INVALID, "h is NULL");
   int st = check_segments(seg, need_k);
   if (st) return st;
-  st = check_scorer(sc, hdtype);
-  if (st) return st;
-  *plan = make_plan(seg->n_seg, seg->rows_per_seg, sc->d, sc->hd);
-  if (!ws || ws_bytes < plan->total)
-    return fail(VSEL_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, plan->total);
-  if (((uintptr_t)h | (uintptr_t)ws | (uintptr_t)sc->wq | (uintptr_t)sc->wk) & 15)
-    return fail(VSEL_ERR_INVALID, "h / workspace / weights must be 16-byte aligned");
-  return VSEL_OK;
+  return check_scorer_workspace(h, hdtype, sc, ws, ws_bytes, [&] {
+    *plan = make_plan(seg->n_seg, seg->rows_per_seg, sc->d, sc->hd);
+    return plan->total;
+  });
 }
 
 extern "C" int vsel_lis_scores(void* stream, const void* h, vsel_dtype hdtype, const vsel_segments* seg,
@@ -102,15 +92,7 @@ extern "C" int vsel_lis_scores(void* stream, const void* h, vsel_dtype hdtype, c
   if (!scores) return fail(VSEL_ERR_INVALID, "scores is NULL");
   hipStream_t s = (hipStream_t)stream;
   VSEL_PROF_BEGIN(s);
-  return with_dtypes(hdtype, sc->wdtype, [&](auto t, auto tw) {
-    using T = decltype(t);
-    const T* hp = (const T*)h;
-    if (!use_small_path(seg, sc, p)) return run_scores<T, decltype(tw)>(s, hp, seg, sc, (char*)ws, p, scores);
-    int rc;
-    if ((rc = run_colsum<T>(s, hp, seg, (int)sc->d, (char*)ws, p))) return rc;
-    if ((rc = run_proj_small(s, seg, sc, (char*)ws, p, nullptr))) return rc;
-    return run_score_small<T>(s, hp, seg, sc, (char*)ws, p, scores, nullptr);
-  });
+  return lis_scores_stage(s, h, hdtype, seg, sc, (char*)ws, p, scores, nullptr, nullptr, use_small_path(seg, sc, p));
 }
 
 extern "C" int vsel_topk_select(void* stream, const float* scores, const vsel_segments* seg, int64_t* idx, float* mask) {
@@ -148,12 +130,7 @@ extern "C" int vsel_lis_select(void* stream, const void* h, vsel_dtype hdtype, c
   if (st) return st;
   if (!out || !idx || !scores) return fail(VSEL_ERR_INVALID, "out / idx / scores is NULL");
   if ((uintptr_t)out & 15) return fail(VSEL_ERR_INVALID, "out must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  VSEL_PROF_BEGIN(s);
-  return with_dtypes(hdtype, sc->wdtype, [&](auto t, auto tw) {
-    using T = decltype(t);
-    return lis_select_impl<T, decltype(tw)>(s, (const T*)h, seg, sc, (char*)ws, p, (T*)out, idx, scores);
-  });
+  return lis_select_impl(stream, h, hdtype, seg, sc, ws, p, out, idx, scores);
 }
 
 // Permuted form: the token rows are stored in a PHYSICAL order (Qwen2.5-VL's window order straight out of the merger) and
@@ -168,14 +145,7 @@ extern "C" int vsel_lis_select_permuted(void* stream, const void* h_physical, vs
   if (st) return st;
   if (!out || !idx || !scores || !logical_to_physical || !physical_to_logical) return fail(VSEL_ERR_INVALID, "NULL pointer");
   if ((uintptr_t)out & 15) return fail(VSEL_ERR_INVALID, "out must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  VSEL_PROF_BEGIN(s);
-  const int64_t* l2p = logical_to_physical;
-  const int64_t* p2l = physical_to_logical;
-  return with_dtypes(hdtype, sc->wdtype, [&](auto t, auto tw) {
-    using T = decltype(t);
-    return lis_select_impl<T, decltype(tw)>(s, (const T*)h_physical, seg, sc, (char*)ws, p, (T*)out, idx, scores, l2p, p2l);
-  });
+  return lis_select_impl(stream, h_physical, hdtype, seg, sc, ws, p, out, idx, scores, logical_to_physical, physical_to_logical);
 }
 
 // Single-sweep form: the producer of the tokens already knows their column sums
@@ -191,12 +161,5 @@ extern "C" int vsel_lis_select_presummed(void* stream, const void* h, vsel_dtype
   if ((logical_to_physical == nullptr) != (physical_to_logical == nullptr))
     return fail(VSEL_ERR_INVALID, "give both row maps or neither");
   if (((uintptr_t)out | (uintptr_t)col_sums) & 15) return fail(VSEL_ERR_INVALID, "out / col_sums must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  VSEL_PROF_BEGIN(s);
-  const int64_t* l2p = logical_to_physical;
-  const int64_t* p2l = physical_to_logical;
-  return with_dtypes(hdtype, sc->wdtype, [&](auto t, auto tw) {
-    using T = decltype(t);
-    return lis_select_impl<T, decltype(tw)>(s, (const T*)h, seg, sc, (char*)ws, p, (T*)out, idx, scores, l2p, p2l, col_sums);
-  });
+  return lis_select_impl(stream, h, hdtype, seg, sc, ws, p, out, idx, scores, logical_to_physical, physical_to_logical, col_sums);
 }

@@ -929,6 +929,32 @@ inline int check_scorer(const vsel_scorer* sc, vsel_dtype hdtype) {
   return VSEL_OK;
 }
 
+// Calls f(T{}) / f(T{}, TW{}) with T the element type of the tokens (hdtype) and TW that of the scorer weights (wdtype): bf16_t or
+// float.  The dtypes have passed check_scorer (or the entry's own "bad dtype" check).
+template <typename F>
+inline int with_dtype(vsel_dtype hdtype, F&& f) {
+  return hdtype == VSEL_BF16 ? f(bf16_t{}) : f(float{});
+}
+template <typename F>
+inline int with_dtypes(vsel_dtype hdtype, vsel_dtype wdtype, F&& f) {
+  return with_dtype(hdtype, [&](auto t) { return wdtype == VSEL_BF16 ? f(t, bf16_t{}) : f(t, float{}); });
+}
+
+// Checks every entry with a scorer and a workspace shares: the scorer, then the workspace size (`need` = the entry's plan, made
+// once the scorer's dims are known good) and the 16-byte alignment of h, workspace and weights (`also`: one more pointer of the
+// entry's that `what` names).
+template <typename Need>
+inline int check_scorer_workspace(const void* h, vsel_dtype hdtype, const vsel_scorer* sc, const void* ws, size_t ws_bytes,
+                                  Need&& need, const char* what = "h / workspace / weights", const void* also = nullptr) {
+  int st = check_scorer(sc, hdtype);
+  if (st) return st;
+  const size_t total = need();
+  if (!ws || ws_bytes < total) return fail(VSEL_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, total);
+  if (((uintptr_t)h | (uintptr_t)ws | (uintptr_t)sc->wq | (uintptr_t)sc->wk | (uintptr_t)also) & 15)
+    return fail(VSEL_ERR_INVALID, "%s must be 16-byte aligned", what);
+  return VSEL_OK;
+}
+
 template <typename T>
 inline int launch_score(hipStream_t st, const T* h, const SegView& sv, const vsel_segments* seg, int d,
                         const float* w, const float* c, int hd, float* scores, const int64_t* out_map = nullptr) {
@@ -1109,15 +1135,12 @@ inline int run_score(hipStream_t st, const T* h, const vsel_segments* seg, const
                          (int)sc->hd, scores, out_map);
 }
 
-template <typename T, typename TW>
-inline int run_scores(hipStream_t st, const T* h, const vsel_segments* seg, const vsel_scorer* sc, char* ws,
-                      const LisPlan& p, float* scores) {
-  int rc = run_colsum<T>(st, h, seg, (int)sc->d, ws, p);
-  if (rc) return rc;
-  rc = run_proj<TW>(st, seg, sc, ws, p);
-  if (rc) return rc;
-  return run_score<T>(st, h, seg, sc, ws, p, scores);
-}
+// The scores stage of every LIS entry (lis.hip, compiled there once): column sums unless the caller supplies col_sums, then the
+// small-batch form (lis_small.h) or the batched form of projections + score sweep -- the same bits either way.  The caller decides
+// `small`: the inference entries pass knob LIS_SMALL_PATH and small_path_ok(), training passes small_path_ok() alone (one segment
+// per call; the knob tunes inference batches and never reaches the training block).  hdtype / sc have passed check_scorer.
+int lis_scores_stage(hipStream_t st, const void* h, vsel_dtype hdtype, const vsel_segments* seg, const vsel_scorer* sc, char* ws,
+                     const LisPlan& p, float* scores, const int64_t* out_map, const float* col_sums, bool small);
 
 inline int launch_select(hipStream_t st, const float* scores, const vsel_segments* seg, int64_t* idx, float* mask) {
   const int64_t maxn = seg->rows_per_seg;            // (= the longest segment for ragged calls)

@@ -591,6 +591,15 @@ inline bool small_path_ok(const vsel_segments* seg, const vsel_scorer* sc, const
          sc->d % 8 == 0 && sc->hd % 8 == 0;
 }
 
+// What the inference entries pass to lis_scores_stage: the form is used up to knob VSEL_KNOB_LIS_SMALL_PATH segments per call.
+// Measured on MI355X (Qwen2.5-VL-7B geometry, us per call, small form vs batched form): 1 image 36.2 vs 51.7, 2 images 43.8 vs
+// 55.8, 3 images 52.2 vs 60.8, 4 images 60.4 vs 65.3, 8 images 102.3 vs 86.2 -- the redundant prologues grow with the segment
+// count, so the default limit is 4.  VSEL_SMALL_PATH=<n> / the knob set the limit (0 = never; at most kSmallMaxSeg).
+static_assert(kSmallMaxSeg == 8, "common.hip clamps VSEL_KNOB_LIS_SMALL_PATH to 8");
+inline bool use_small_path(const vsel_segments* seg, const vsel_scorer* sc, const LisPlan& p) {
+  return seg->n_seg <= knob(VSEL_KNOB_LIS_SMALL_PATH) && small_path_ok(seg, sc, p);
+}
+
 // sweep 1 partials (or the producer's column sums) -> part2 slabs + c partials: two launches
 inline int run_proj_small(hipStream_t st, const vsel_segments* seg, const vsel_scorer* sc, char* ws, const LisPlan& p,
                           const float* col_sums) {

@@ -312,13 +312,23 @@ __global__ __launch_bounds__(kSpliceThreads) void select_splice_small_kernel(
   }
 }
 
+// Host-side argument block of the two entries: the prompts as given, and where the results go (filled once per call, never
+// passed to a kernel: the launches below unpack it).  Embedding pointers are of the token dtype.
+struct SpliceIO {
+  const int64_t* ids; int64_t total_len; const int32_t* cu_seqlens; int64_t max_len_out; int64_t visual_id;
+  const void* embeds; const int64_t* pos; int64_t pos_rows; const int64_t* mask;
+  int64_t* idx; int64_t* sel; int64_t* new_ids; void* new_embeds; int64_t* new_pos; int64_t* new_mask;
+  int32_t* cu_out; int32_t* src_scratch; int32_t* stats;
+  SoftOut soft;
+};
+
 template <typename T>
 static int launch_select_splice(hipStream_t st, const T* h, int d, const vsel_segments* seg, const float* scores,
-                                const int64_t* l2p, const int64_t* ids, const int32_t* cu_seqlens, int64_t total_len,
-                                int64_t max_len_out, int64_t visual_id, const T* embeds, const int64_t* pos, int pos_rows,
-                                const int64_t* mask, int64_t* idx, int64_t* sel, int64_t* new_ids, T* new_embeds,
-                                int64_t* new_pos, int64_t* new_mask, int32_t* cu_out, int32_t* src_scratch, int32_t* stats,
-                                int64_t l_out, SoftOut soft) {
+                                const int64_t* l2p, const SpliceIO& io, int64_t l_out) {
+  const T* embeds = (const T*)io.embeds;
+  T* new_embeds = (T*)io.new_embeds;
+  const int pos_rows = (int)io.pos_rows;
+  const SoftOut soft = io.soft;
   const SegView sv = make_view(seg);
   const int S = (int)seg->n_seg;
   const int64_t maxn = seg->rows_per_seg;
@@ -335,14 +345,15 @@ static int launch_select_splice(hipStream_t st, const T* h, int d, const vsel_se
   const SoftOut soft_k = soft_inside ? soft : SoftOut{nullptr, nullptr};
   if (fused) {
     const int single = S == 1;
-    if (!single && hipMemsetAsync(stats, 0, 4 * sizeof(int32_t), st) != hipSuccess) return fail(VSEL_ERR_HIP, "hipMemsetAsync(stats)");
+    if (!single && hipMemsetAsync(io.stats, 0, 4 * sizeof(int32_t), st) != hipSuccess) return fail(VSEL_ERR_HIP, "hipMemsetAsync(stats)");
     int64_t rpb = kSelectSpliceMaxRows;
-    while (rpb > 2 && S * cdiv(max_len_out, rpb) < 128) rpb >>= 1;
-    const dim3 grid((unsigned)std::max<int64_t>(1, cdiv(max_len_out, rpb)) + (soft_inside ? 1u : 0u), (unsigned)S);
+    while (rpb > 2 && S * cdiv(io.max_len_out, rpb) < 128) rpb >>= 1;
+    const dim3 grid((unsigned)std::max<int64_t>(1, cdiv(io.max_len_out, rpb)) + (soft_inside ? 1u : 0u), (unsigned)S);
 #define VSEL_SS_LAUNCH(KPT)                                                                                                 \
-    VSEL_LAUNCH((select_splice_small_kernel<T, KPT>), grid, dim3(kSpliceThreads), 0, st, h, scores, sv, d, l2p, ids,   \
-                       cu_seqlens, S, (int)total_len, visual_id, embeds, pos, pos_rows, mask, idx, sel, new_ids, new_embeds, \
-                       new_pos, new_mask, cu_out, stats, (int)l_out, (int)rpb, (int)seg->total_rows, single, soft_k)
+    VSEL_LAUNCH((select_splice_small_kernel<T, KPT>), grid, dim3(kSpliceThreads), 0, st, h, scores, sv, d, l2p, io.ids,       \
+                io.cu_seqlens, S, (int)io.total_len, io.visual_id, embeds, io.pos, pos_rows, io.mask, io.idx, io.sel, io.new_ids, \
+                new_embeds, io.new_pos, io.new_mask, io.cu_out, io.stats, (int)l_out, (int)rpb, (int)seg->total_rows, single,   \
+                soft_k)
     if (maxn <= 4 * kSpliceThreads) VSEL_SS_LAUNCH(4);
     else if (maxn <= 8 * kSpliceThreads) VSEL_SS_LAUNCH(8);
     else VSEL_SS_LAUNCH(32);
@@ -350,61 +361,44 @@ static int launch_select_splice(hipStream_t st, const T* h, int d, const vsel_se
     VSEL_AFTER_LAUNCH(st, "select_splice_small_kernel");
     return soft_after();
   }
-  int rc = launch_select(st, scores, seg, idx, nullptr);
+  int rc = launch_select(st, scores, seg, io.idx, nullptr);
   if (rc) return rc;
-  if (hipMemsetAsync(stats, 0, 4 * sizeof(int32_t), st) != hipSuccess) return fail(VSEL_ERR_HIP, "hipMemsetAsync(stats)");
-  if (l_out > 0 && hipMemsetAsync(src_scratch, 0x7f, (size_t)l_out * sizeof(int32_t), st) != hipSuccess)
+  if (hipMemsetAsync(io.stats, 0, 4 * sizeof(int32_t), st) != hipSuccess) return fail(VSEL_ERR_HIP, "hipMemsetAsync(stats)");
+  if (l_out > 0 && hipMemsetAsync(io.src_scratch, 0x7f, (size_t)l_out * sizeof(int32_t), st) != hipSuccess)
     return fail(VSEL_ERR_HIP, "hipMemsetAsync(src)");
   const size_t lds = (size_t)((maxn + 31) / 32) * 4 + 16;
-  VSEL_LAUNCH(splice_index_seg_kernel, dim3((unsigned)S), dim3(kSpliceThreads), lds, st, ids, cu_seqlens, sv, S,
-                     (int)total_len, visual_id, idx, l2p, pos, pos_rows, mask, sel, new_ids, new_pos, new_mask, src_scratch,
-                     cu_out, stats, (int)l_out);
+  VSEL_LAUNCH(splice_index_seg_kernel, dim3((unsigned)S), dim3(kSpliceThreads), lds, st, io.ids, io.cu_seqlens, sv, S,
+              (int)io.total_len, io.visual_id, io.idx, l2p, io.pos, pos_rows, io.mask, io.sel, io.new_ids, io.new_pos, io.new_mask,
+              io.src_scratch, io.cu_out, io.stats, (int)l_out);
   VSEL_AFTER_LAUNCH(st, "splice_index_seg_kernel");
   if (l_out > 0) {
     const unsigned blocks = (unsigned)std::min<int64_t>(cdiv(l_out, 4), 2048);
-    VSEL_LAUNCH((splice_embed_kernel<T>), dim3(blocks), dim3(256), 0, st, embeds, h, src_scratch, (int)l_out, d,
-                       (int)total_len, (int)seg->total_rows, new_embeds);
+    VSEL_LAUNCH((splice_embed_kernel<T>), dim3(blocks), dim3(256), 0, st, embeds, h, io.src_scratch, (int)l_out, d,
+                       (int)io.total_len, (int)seg->total_rows, new_embeds);
     VSEL_AFTER_LAUNCH(st, "splice_embed_kernel");
   }
   return soft_after();
-}
-
-template <typename T, typename TW>
-static int scores_for_splice(hipStream_t st, const T* h, const vsel_segments* seg, const vsel_scorer* sc, char* ws,
-                             const LisPlan& p, float* scores, const int64_t* p2l, const float* col_sums) {
-  int rc = VSEL_OK;
-  if (!col_sums && (rc = run_colsum<T>(st, h, seg, (int)sc->d, ws, p))) return rc;
-  if (seg->n_seg <= knob(VSEL_KNOB_LIS_SMALL_PATH) && small_path_ok(seg, sc, p)) {
-    if ((rc = run_proj_small(st, seg, sc, ws, p, col_sums))) return rc;
-    return run_score_small<T>(st, h, seg, sc, ws, p, scores, p2l);
-  }
-  if ((rc = run_proj<TW>(st, seg, sc, ws, p, col_sums))) return rc;
-  return run_score<T>(st, h, seg, sc, ws, p, scores, p2l);
 }
 
 }  // namespace vsel
 
 using namespace vsel;
 
-// shared argument checks of the two entry points
-static int splice_args_check(const void* h, vsel_dtype hdtype, const vsel_segments* seg, const int64_t* input_ids, int64_t total_len,
-                             const int32_t* cu_seqlens, int64_t max_len_out, const void* inputs_embeds, const int64_t* position_ids,
-                             int64_t pos_rows, const int64_t* attention_mask, const int64_t* idx, const float* scores,
-                             const int64_t* selected_indices, const int64_t* new_input_ids, const void* new_inputs_embeds,
-                             const int64_t* new_position_ids, const int64_t* new_attention_mask, const int32_t* cu_seqlens_out,
-                             const int32_t* src_scratch, const int32_t* stats, int64_t d, int64_t* l_out) {
-  if (!h || !input_ids || !inputs_embeds || !idx || !scores || !selected_indices || !new_input_ids || !new_inputs_embeds ||
-      !src_scratch || !stats)
+// shared argument checks of the two entry points; *l_out = the packed output length
+static int splice_args_check(const void* h, vsel_dtype hdtype, const vsel_segments* seg, const float* scores, int64_t d,
+                             const SpliceIO& io, int64_t* l_out) {
+  if (!h || !io.ids || !io.embeds || !io.idx || !scores || !io.sel || !io.new_ids || !io.new_embeds || !io.src_scratch || !io.stats)
     return fail(VSEL_ERR_INVALID, "NULL pointer");
   int rc = check_segments_impl(seg, true);
   if (rc) return rc;
   if (seg->n_seg > 65535) return fail(VSEL_ERR_UNSUPPORTED, "more than 65535 prompts");
-  if (seg->n_seg > 1 && (!cu_seqlens || !cu_seqlens_out))
+  if (seg->n_seg > 1 && (!io.cu_seqlens || !io.cu_out))
     return fail(VSEL_ERR_INVALID, "several prompts need cu_seqlens / cu_seqlens_out");
-  if (pos_rows < 0 || pos_rows > 4 || (pos_rows > 0 && (!position_ids || !new_position_ids)))
+  if (io.pos_rows < 0 || io.pos_rows > 4 || (io.pos_rows > 0 && (!io.pos || !io.new_pos)))
     return fail(VSEL_ERR_INVALID, "bad position_ids arguments");
-  if ((attention_mask == nullptr) != (new_attention_mask == nullptr)) return fail(VSEL_ERR_INVALID, "attention_mask in/out mismatch");
+  if ((io.mask == nullptr) != (io.new_mask == nullptr)) return fail(VSEL_ERR_INVALID, "attention_mask in/out mismatch");
   if (hdtype != VSEL_BF16 && hdtype != VSEL_F32) return fail(VSEL_ERR_INVALID, "bad dtype");
+  const int64_t total_len = io.total_len, max_len_out = io.max_len_out;
   *l_out = total_len - seg->total_rows + seg->total_out;
   if (total_len < 1 || total_len >= (1ll << 31) || seg->total_rows > total_len || seg->total_rows >= (1ll << 31) || *l_out < 1 ||
       max_len_out < 1 || max_len_out > *l_out)
@@ -413,29 +407,19 @@ static int splice_args_check(const void* h, vsel_dtype hdtype, const vsel_segmen
   if (seg->n_seg == 1 && max_len_out != *l_out)
     return fail(VSEL_ERR_INVALID, "one prompt: max_len_out (%lld) must be its L' (%lld)", (long long)max_len_out, (long long)*l_out);
   if (seg->rows_per_seg > kMaxVisualBits) return fail(VSEL_ERR_UNSUPPORTED, "more than %d visual tokens in one prompt", kMaxVisualBits);
-  if (((uintptr_t)h | (uintptr_t)inputs_embeds | (uintptr_t)new_inputs_embeds) & 15)
+  if (((uintptr_t)h | (uintptr_t)io.embeds | (uintptr_t)io.new_embeds) & 15)
     return fail(VSEL_ERR_INVALID, "h / embeddings must be 16-byte aligned");
   const int vec = hdtype == VSEL_BF16 ? 8 : 4;
   if (d < vec || d % vec) return fail(VSEL_ERR_UNSUPPORTED, "token width must be a multiple of %d", vec);
   return VSEL_OK;
 }
 
-static int select_splice_dispatch(hipStream_t st, const void* h, vsel_dtype hdtype, int64_t d, const vsel_segments* seg,
-                                  const float* scores, const int64_t* l2p, const int64_t* input_ids, const int32_t* cu_seqlens,
-                                  int64_t total_len, int64_t max_len_out, int64_t visual_token_id, const void* inputs_embeds,
-                                  const int64_t* position_ids, int64_t pos_rows, const int64_t* attention_mask, int64_t* idx,
-                                  int64_t* selected_indices, int64_t* new_input_ids, void* new_inputs_embeds,
-                                  int64_t* new_position_ids, int64_t* new_attention_mask, int32_t* cu_seqlens_out,
-                                  int32_t* src_scratch, int32_t* stats, int64_t l_out, SoftOut soft) {
-  if (hdtype == VSEL_BF16)
-    return launch_select_splice<bf16_t>(st, (const bf16_t*)h, (int)d, seg, scores, l2p, input_ids, cu_seqlens, total_len,
-                                        max_len_out, visual_token_id, (const bf16_t*)inputs_embeds, position_ids, (int)pos_rows,
-                                        attention_mask, idx, selected_indices, new_input_ids, (bf16_t*)new_inputs_embeds,
-                                        new_position_ids, new_attention_mask, cu_seqlens_out, src_scratch, stats, l_out, soft);
-  return launch_select_splice<float>(st, (const float*)h, (int)d, seg, scores, l2p, input_ids, cu_seqlens, total_len, max_len_out,
-                                     visual_token_id, (const float*)inputs_embeds, position_ids, (int)pos_rows, attention_mask, idx,
-                                     selected_indices, new_input_ids, (float*)new_inputs_embeds, new_position_ids,
-                                     new_attention_mask, cu_seqlens_out, src_scratch, stats, l_out, soft);
+static int select_splice(hipStream_t st, const void* h, vsel_dtype hdtype, int64_t d, const vsel_segments* seg, const float* scores,
+                         const int64_t* l2p, const SpliceIO& io, int64_t l_out) {
+  return with_dtype(hdtype, [&](auto t) {
+    using T = decltype(t);
+    return launch_select_splice<T>(st, (const T*)h, (int)d, seg, scores, l2p, io, l_out);
+  });
 }
 
 extern "C" int vsel_lis_select_splice(void* stream, const void* h, vsel_dtype hdtype, const vsel_segments* seg,
@@ -449,32 +433,25 @@ extern "C" int vsel_lis_select_splice(void* stream, const void* h, vsel_dtype hd
                                       int32_t* src_scratch, int32_t* stats, float* soft_ps, float* soft_ts) {
   if (!scorer) return fail(VSEL_ERR_INVALID, "scorer is NULL");
   if ((soft_ps == nullptr) != (soft_ts == nullptr)) return fail(VSEL_ERR_INVALID, "give both soft_ps and soft_ts or neither");
+  const SpliceIO io{input_ids, total_len, cu_seqlens, max_len_out, visual_token_id, inputs_embeds, position_ids, pos_rows,
+                    attention_mask, idx, selected_indices, new_input_ids, new_inputs_embeds, new_position_ids, new_attention_mask,
+                    cu_seqlens_out, src_scratch, stats, SoftOut{soft_ps, soft_ts}};
   int64_t l_out = 0;
-  int rc = splice_args_check(h, hdtype, seg, input_ids, total_len, cu_seqlens, max_len_out, inputs_embeds, position_ids, pos_rows,
-                             attention_mask, idx, scores, selected_indices, new_input_ids, new_inputs_embeds, new_position_ids,
-                             new_attention_mask, cu_seqlens_out, src_scratch, stats, scorer->d, &l_out);
+  int rc = splice_args_check(h, hdtype, seg, scores, scorer->d, io, &l_out);
   if (rc) return rc;
   if ((logical_to_physical == nullptr) != (physical_to_logical == nullptr)) return fail(VSEL_ERR_INVALID, "give both row maps or neither");
-  if ((rc = check_scorer(scorer, hdtype))) return rc;
-  const LisPlan p = make_plan(seg->n_seg, seg->rows_per_seg, scorer->d, scorer->hd);
-  if (!workspace || workspace_bytes < p.total) return fail(VSEL_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, p.total);
-  if (((uintptr_t)workspace | (uintptr_t)scorer->wq | (uintptr_t)scorer->wk | (uintptr_t)col_sums) & 15)
-    return fail(VSEL_ERR_INVALID, "workspace / weights / col_sums must be 16-byte aligned");
+  LisPlan p;
+  rc = check_scorer_workspace(h, hdtype, scorer, workspace, workspace_bytes, [&] {
+    p = make_plan(seg->n_seg, seg->rows_per_seg, scorer->d, scorer->hd);
+    return p.total;
+  }, "workspace / weights / col_sums", col_sums);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   VSEL_PROF_BEGIN(st);
-  char* ws = (char*)workspace;
-  const int64_t* p2l = physical_to_logical;
-  if (hdtype == VSEL_BF16)
-    rc = scorer->wdtype == VSEL_BF16 ? scores_for_splice<bf16_t, bf16_t>(st, (const bf16_t*)h, seg, scorer, ws, p, scores, p2l, col_sums)
-                                     : scores_for_splice<bf16_t, float>(st, (const bf16_t*)h, seg, scorer, ws, p, scores, p2l, col_sums);
-  else
-    rc = scorer->wdtype == VSEL_BF16 ? scores_for_splice<float, bf16_t>(st, (const float*)h, seg, scorer, ws, p, scores, p2l, col_sums)
-                                     : scores_for_splice<float, float>(st, (const float*)h, seg, scorer, ws, p, scores, p2l, col_sums);
+  rc = lis_scores_stage(st, h, hdtype, seg, scorer, (char*)workspace, p, scores, physical_to_logical, col_sums,
+                        use_small_path(seg, scorer, p));
   if (rc) return rc;
-  return select_splice_dispatch(st, h, hdtype, scorer->d, seg, scores, logical_to_physical, input_ids, cu_seqlens, total_len,
-                                max_len_out, visual_token_id, inputs_embeds, position_ids, pos_rows, attention_mask, idx,
-                                selected_indices, new_input_ids, new_inputs_embeds, new_position_ids, new_attention_mask,
-                                cu_seqlens_out, src_scratch, stats, l_out, SoftOut{soft_ps, soft_ts});
+  return select_splice(st, h, hdtype, scorer->d, seg, scores, logical_to_physical, io, l_out);
 }
 
 extern "C" int vsel_topk_select_splice(void* stream, const void* h, vsel_dtype hdtype, int64_t d, const vsel_segments* seg,
@@ -486,15 +463,13 @@ extern "C" int vsel_topk_select_splice(void* stream, const void* h, vsel_dtype h
                                        int64_t* new_attention_mask, int32_t* cu_seqlens_out, int32_t* src_scratch, int32_t* stats,
                                        float* soft_ps, float* soft_ts) {
   if ((soft_ps == nullptr) != (soft_ts == nullptr)) return fail(VSEL_ERR_INVALID, "give both soft_ps and soft_ts or neither");
+  const SpliceIO io{input_ids, total_len, cu_seqlens, max_len_out, visual_token_id, inputs_embeds, position_ids, pos_rows,
+                    attention_mask, idx, selected_indices, new_input_ids, new_inputs_embeds, new_position_ids, new_attention_mask,
+                    cu_seqlens_out, src_scratch, stats, SoftOut{soft_ps, soft_ts}};
   int64_t l_out = 0;
-  int rc = splice_args_check(h, hdtype, seg, input_ids, total_len, cu_seqlens, max_len_out, inputs_embeds, position_ids, pos_rows,
-                             attention_mask, idx, scores, selected_indices, new_input_ids, new_inputs_embeds, new_position_ids,
-                             new_attention_mask, cu_seqlens_out, src_scratch, stats, d, &l_out);
+  int rc = splice_args_check(h, hdtype, seg, scores, d, io, &l_out);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   VSEL_PROF_BEGIN(st);
-  return select_splice_dispatch(st, h, hdtype, d, seg, scores, logical_to_physical, input_ids, cu_seqlens, total_len, max_len_out,
-                                visual_token_id, inputs_embeds, position_ids, pos_rows, attention_mask, idx, selected_indices,
-                                new_input_ids, new_inputs_embeds, new_position_ids, new_attention_mask, cu_seqlens_out, src_scratch,
-                                stats, l_out, SoftOut{soft_ps, soft_ts});
+  return select_splice(st, h, hdtype, d, seg, scores, logical_to_physical, io, l_out);
 }

@@ -747,19 +747,12 @@ static TrainPlan make_train_plan(int64_t n, int64_t d, int64_t hd) {
   return t;
 }
 
-template <typename T, typename TW>
-static int train_fwd_impl(hipStream_t st, const T* h, int64_t n, int64_t k, const vsel_scorer* sc, char* ws,
+template <typename T>
+static int train_fwd_impl(hipStream_t st, const T* h, vsel_dtype hdtype, int64_t n, int64_t k, const vsel_scorer* sc, char* ws,
                           const TrainPlan& tp, T* h_new, float* ps, float* y, float* scores, float* ts, float* bce) {
   vsel_segments seg{1, n, n, k, k, nullptr, nullptr};
-  int rc;
-  if (small_path_ok(&seg, sc, tp.lis)) {
-    // one segment: the four-launch small-batch form of the scores (lis_small.h; bit-identical to run_scores)
-    if ((rc = run_colsum<T>(st, h, &seg, (int)sc->d, ws, tp.lis))) return rc;
-    if ((rc = run_proj_small(st, &seg, sc, ws, tp.lis, nullptr))) return rc;
-    rc = run_score_small<T>(st, h, &seg, sc, ws, tp.lis, scores, nullptr);
-  } else {
-    rc = run_scores<T, TW>(st, h, &seg, sc, ws, tp.lis, scores);
-  }
+  // one segment: the small-batch form of the scores whenever the shapes allow it (whatever knob LIS_SMALL_PATH says)
+  int rc = lis_scores_stage(st, h, hdtype, &seg, sc, ws, tp.lis, scores, nullptr, nullptr, small_path_ok(&seg, sc, tp.lis));
   if (rc) return rc;
   const int d = (int)sc->d;
   if (n <= 4096) {
@@ -930,22 +923,11 @@ static int train_checks(const void* h, vsel_dtype hdtype, int64_t n, const vsel_
                         TrainPlan* tp) {
   if (!h) return fail(VSEL_ERR_INVALID, "h is NULL");
   if (n < 1 || n >= (1ll << 31)) return fail(VSEL_ERR_INVALID, "bad n=%lld", (long long)n);
-  int st = check_scorer(sc, hdtype);
-  if (st) return st;
-  *tp = make_train_plan(n, sc->d, sc->hd);
-  if (!ws || ws_bytes < tp->total) return fail(VSEL_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, tp->total);
-  if (((uintptr_t)h | (uintptr_t)ws | (uintptr_t)sc->wq | (uintptr_t)sc->wk) & 15)
-    return fail(VSEL_ERR_INVALID, "h / workspace / weights must be 16-byte aligned");
-  return VSEL_OK;
+  return check_scorer_workspace(h, hdtype, sc, ws, ws_bytes, [&] {
+    *tp = make_train_plan(n, sc->d, sc->hd);
+    return tp->total;
+  });
 }
-
-#define VSEL_DISPATCH2(hdtype, wdtype, CALL)                                        \
-  do {                                                                              \
-    if ((hdtype) == VSEL_BF16 && (wdtype) == VSEL_BF16) { using T = bf16_t; using TW = bf16_t; return CALL; } \
-    if ((hdtype) == VSEL_BF16 && (wdtype) == VSEL_F32) { using T = bf16_t; using TW = float; return CALL; }   \
-    if ((hdtype) == VSEL_F32 && (wdtype) == VSEL_BF16) { using T = float; using TW = bf16_t; return CALL; }   \
-    { using T = float; using TW = float; return CALL; }                             \
-  } while (0)
 
 extern "C" int vsel_lis_train_fwd(void* stream, const void* h, vsel_dtype hdtype, int64_t n, int64_t k,
                                   const vsel_scorer* sc, void* ws, size_t ws_bytes, void* h_new, float* ps, float* y,
@@ -958,8 +940,10 @@ extern "C" int vsel_lis_train_fwd(void* stream, const void* h, vsel_dtype hdtype
   if (!(0 < k && k < n)) return fail(VSEL_ERR_INVALID, "training needs 0 < k < n (k=%lld, n=%lld)", (long long)k, (long long)n);
   hipStream_t s = (hipStream_t)stream;
   VSEL_PROF_BEGIN(s);
-  VSEL_DISPATCH2(hdtype, sc->wdtype,
-                 (train_fwd_impl<T, TW>(s, (const T*)h, n, k, sc, (char*)ws, tp, (T*)h_new, ps, y, scores, ts, bce)));
+  return with_dtype(hdtype, [&](auto t) {
+    using T = decltype(t);
+    return train_fwd_impl<T>(s, (const T*)h, hdtype, n, k, sc, (char*)ws, tp, (T*)h_new, ps, y, scores, ts, bce);
+  });
 }
 
 extern "C" int vsel_lis_train_bwd(void* stream, const void* d_hnew, const void* h, vsel_dtype hdtype, int64_t n,
@@ -973,9 +957,11 @@ extern "C" int vsel_lis_train_bwd(void* stream, const void* d_hnew, const void* 
   if (sc->d % 4) return fail(VSEL_ERR_UNSUPPORTED, "D must be a multiple of 4");
   hipStream_t s = (hipStream_t)stream;
   VSEL_PROF_BEGIN(s);
-  VSEL_DISPATCH2(hdtype, sc->wdtype,
-                 (train_bwd_impl<T, TW>(s, (const T*)d_hnew, (const T*)h, n, sc, ps, y, scores, ts, d_ps_ext, dl_dbce,
-                                        (char*)ws, tp, dwq, dbq, dwk, dbk, (T*)dh)));
+  return with_dtypes(hdtype, sc->wdtype, [&](auto t, auto tw) {
+    using T = decltype(t);
+    return train_bwd_impl<T, decltype(tw)>(s, (const T*)d_hnew, (const T*)h, n, sc, ps, y, scores, ts, d_ps_ext, dl_dbce,
+                                           (char*)ws, tp, dwq, dbq, dwk, dbk, (T*)dh);
+  });
 }
 
 extern "C" int vsel_lis_train_bwd_factors(void* stream, const void* d_hnew, const void* h, vsel_dtype hdtype, int64_t n,
@@ -989,9 +975,11 @@ extern "C" int vsel_lis_train_bwd_factors(void* stream, const void* d_hnew, cons
   if (sc->d % 4 || sc->hd % 4) return fail(VSEL_ERR_UNSUPPORTED, "D and Hd must be multiples of 4");
   hipStream_t s = (hipStream_t)stream;
   VSEL_PROF_BEGIN(s);
-  VSEL_DISPATCH2(hdtype, sc->wdtype,
-                 (train_bwd_impl<T, TW>(s, (const T*)d_hnew, (const T*)h, n, sc, ps, y, scores, ts, d_ps_ext, dl_dbce,
-                                        (char*)ws, tp, nullptr, dbq, nullptr, dbk, (T*)dh, factors)));
+  return with_dtypes(hdtype, sc->wdtype, [&](auto t, auto tw) {
+    using T = decltype(t);
+    return train_bwd_impl<T, decltype(tw)>(s, (const T*)d_hnew, (const T*)h, n, sc, ps, y, scores, ts, d_ps_ext, dl_dbce,
+                                           (char*)ws, tp, nullptr, dbq, nullptr, dbk, (T*)dh, factors);
+  });
 }
 
 extern "C" int vsel_lis_factors_to_grads(void* stream, const float* payload, int64_t n_rows, int64_t hd, int64_t d, float scale,
@@ -1018,7 +1006,9 @@ extern "C" int vsel_lis_scores_bwd(void* stream, const float* g, const void* h, 
   if (sc->d % 4) return fail(VSEL_ERR_UNSUPPORTED, "D must be a multiple of 4");
   hipStream_t s = (hipStream_t)stream;
   VSEL_PROF_BEGIN(s);
-  VSEL_DISPATCH2(hdtype, sc->wdtype,
-                 (scores_bwd_impl<T, TW>(s, g, (const T*)h, n, sc, (char*)ws, tp, dwq, dbq, dwk, dbk, (T*)dh, (const T*)nullptr,
-                                         (const float*)nullptr)));
+  return with_dtypes(hdtype, sc->wdtype, [&](auto t, auto tw) {
+    using T = decltype(t);
+    return scores_bwd_impl<T, decltype(tw)>(s, g, (const T*)h, n, sc, (char*)ws, tp, dwq, dbq, dwk, dbk, (T*)dh, (const T*)nullptr,
+                                            (const float*)nullptr);
+  });
 }

@@ -103,13 +103,16 @@ def _uniform_segments(b: int, n: int, k: int) -> N.Segments:
     return N.Segments(b, n, b * n, k, b * k, None, None)
 
 
+def _cu_int32(lens: Sequence[int], device) -> torch.Tensor:
+    """Exclusive prefix sums of lens as the C-ABI reads them: int32 [len(lens) + 1] on `device`, summed in Python ints, no sync."""
+    return torch.tensor(list(itertools.accumulate(lens, initial=0)), dtype=torch.int32).to(device, non_blocking=True)
+
+
 def _ragged_segments(seg_lens: Sequence[int], ks: Sequence[int], device) -> Tuple[N.Segments, torch.Tensor, torch.Tensor]:
     key = (tuple(seg_lens), tuple(ks), str(device))
     hit = _seg_cache.get(key)
     if hit is None:
-        cu_r = torch.tensor([0] + list(seg_lens), dtype=torch.int64).cumsum(0).to(torch.int32)
-        cu_o = torch.tensor([0] + list(ks), dtype=torch.int64).cumsum(0).to(torch.int32)
-        hit = (cu_r.to(device), cu_o.to(device), int(cu_r[-1]), int(cu_o[-1]))
+        hit = (_cu_int32(seg_lens, device), _cu_int32(ks, device), sum(seg_lens), sum(ks))
         if len(_seg_cache) > 256:
             _seg_cache.clear()
         _seg_cache[key] = hit
@@ -134,6 +137,7 @@ def _as_bnd(h: torch.Tensor) -> Tuple[int, int, int]:
 # inference
 # ------------------------------------------------------------------------------------------------
 
+@_device_guard
 def lis_scores(h, wq, bq, wk, bk) -> torch.Tensor:
     """TransformerScorer.forward: h [B,N,D] (or [N,D]) -> fp32 scores [B,N] (or [N])."""
     dev = _dev(h, wq, bq, wk, bk)
@@ -150,12 +154,29 @@ def lis_scores(h, wq, bq, wk, bk) -> torch.Tensor:
     return scores
 
 
-def lis_select(h, wq, bq, wk, bk, k: int):
-    """Fused score + hard top-k + gather.  h [B,N,D] or [N,D] -> (out [B,k,D], idx int64 [B,k] ascending, scores fp32 [B,N])."""
-    dev = _dev(h, wq, bq, wk, bk)
+def _row_map(m, name: str, rows: int):
+    """A row permutation map as the C-ABI reads it: int64, contiguous, one entry per token row (or None)."""
+    if m is None:
+        return None
+    if m.dtype != torch.int64:
+        raise TypeError(f"{name} must be int64 (got {m.dtype})")
+    if m.numel() != rows:
+        raise ValueError(f"{name} must have one entry per token row ({rows}), got {m.numel()}")
+    return m.contiguous()
+
+
+def _lis_select_uniform(entry: str, h, wq, bq, wk, bk, k: int, l2p=None, p2l=None, col_sums=None):
+    """The uniform select family (entry: vsel_lis_select / _permuted / _presummed): shape checks, segments, workspace, the three
+    outputs and the call."""
+    dev = _dev(h, col_sums, wq, bq, wk, bk, l2p, p2l)
     b, n, d = _as_bnd(h)
+    if col_sums is not None and (col_sums.dtype != torch.float32 or col_sums.numel() != b * d or not col_sums.is_contiguous()):
+        raise ValueError("col_sums must be contiguous float32 with one row of D sums per segment")
+    if (l2p is None) != (p2l is None):
+        raise ValueError("give both permutation maps or neither")
+    l2p, p2l = _row_map(l2p, "logical_to_physical", b * n), _row_map(p2l, "physical_to_logical", b * n)
     sc = _scorer(wq, bq, wk, bk)
-    if sc.d != d:
+    if sc.d != d:             # the library takes the token width from the scorer: narrower tokens would be read past their end
         raise ValueError(f"token width {d} != scorer in_features {sc.d}")
     seg = _uniform_segments(b, n, int(k))
     lib = N.lib()
@@ -164,35 +185,32 @@ def lis_select(h, wq, bq, wk, bk, k: int):
     out = torch.empty(*lead, k, d, dtype=h.dtype, device=dev)
     idx = torch.empty(*lead, k, dtype=torch.int64, device=dev)
     scores = torch.empty(*lead, n, dtype=torch.float32, device=dev)
-    N.check(lib.vsel_lis_select(_stream(), h.data_ptr(), _code(h), C.byref(seg), C.byref(sc), ws.data_ptr(), ws.numel(),
-                                out.data_ptr(), idx.data_ptr(), scores.data_ptr()))
+    head = (_stream(), h.data_ptr(), _code(h), C.byref(seg), C.byref(sc))
+    tail = (out.data_ptr(), idx.data_ptr(), scores.data_ptr())
+    if entry == "vsel_lis_select":
+        N.check(lib.vsel_lis_select(*head, ws.data_ptr(), ws.numel(), *tail))
+    elif entry == "vsel_lis_select_permuted":
+        N.check(lib.vsel_lis_select_permuted(*head, ws.data_ptr(), ws.numel(), l2p.data_ptr(), p2l.data_ptr(), *tail))
+    else:
+        N.check(lib.vsel_lis_select_presummed(*head, col_sums.data_ptr(), ws.data_ptr(), ws.numel(), _p(l2p), _p(p2l), *tail))
     return out, idx, scores
 
 
+@_device_guard
+def lis_select(h, wq, bq, wk, bk, k: int):
+    """Fused score + hard top-k + gather.  h [B,N,D] or [N,D] -> (out [B,k,D], idx int64 [B,k] ascending, scores fp32 [B,N])."""
+    return _lis_select_uniform("vsel_lis_select", h, wq, bq, wk, bk, k)
+
+
+@_device_guard
 def lis_select_permuted(h_physical, logical_to_physical, physical_to_logical, wq, bq, wk, bk, k: int):
     """lis_select on h_physical[logical_to_physical] without materialising that gather (Qwen2.5-VL window order ->
     natural order: logical_to_physical = reverse_indices, physical_to_logical = window_index).  h [N,D] or [B,N,D];
     maps int64 with GLOBAL row numbers."""
-    dev = _dev(h_physical, logical_to_physical, physical_to_logical, wq, bq, wk, bk)
-    b, n, d = _as_bnd(h_physical)
-    if logical_to_physical.dtype != torch.int64 or physical_to_logical.dtype != torch.int64:
-        raise TypeError("permutation maps must be int64")
-    if logical_to_physical.numel() != b * n or physical_to_logical.numel() != b * n:
-        raise ValueError("permutation maps must have one entry per token row")
-    sc = _scorer(wq, bq, wk, bk)
-    seg = _uniform_segments(b, n, int(k))
-    lib = N.lib()
-    ws = _workspace(lib.vsel_lis_workspace_bytes(C.byref(seg), d, sc.hd), dev)
-    lead = h_physical.shape[:-2]
-    out = torch.empty(*lead, k, d, dtype=h_physical.dtype, device=dev)
-    idx = torch.empty(*lead, k, dtype=torch.int64, device=dev)
-    scores = torch.empty(*lead, n, dtype=torch.float32, device=dev)
-    N.check(lib.vsel_lis_select_permuted(_stream(), h_physical.data_ptr(), _code(h_physical), C.byref(seg), C.byref(sc),
-                                         ws.data_ptr(), ws.numel(), logical_to_physical.data_ptr(),
-                                         physical_to_logical.data_ptr(), out.data_ptr(), idx.data_ptr(), scores.data_ptr()))
-    return out, idx, scores
+    return _lis_select_uniform("vsel_lis_select_permuted", h_physical, wq, bq, wk, bk, k, logical_to_physical, physical_to_logical)
 
 
+@_device_guard
 def gelu_colsum(x: torch.Tensor, n_seg: int = 1, sums: bool = True):
     """y = GELU(x) (erf form, as nn.GELU()) and the per-segment column sums of y, in one pass.  x [R, C] (n_seg equal
     segments of R / n_seg rows) -> (y [R, C] same dtype, col_sums fp32 [n_seg, C]).  sums=False: the same kernel without the
@@ -216,6 +234,7 @@ def gelu_colsum(x: torch.Tensor, n_seg: int = 1, sums: bool = True):
     return y, col_sums
 
 
+@_device_guard
 def colsum_linear(col_sums_in: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], rows_per_seg: int):
     """sum_rows(H) from sum_rows(G) for H = G W^T + b on the stored weight (vsel_colsum_linear): col_sums_in fp32 [S, Cin],
     weight [Cout, Cin] (bf16 / fp32), bias [Cout] or None, rows_per_seg = N -> fp32 [S, Cout] = col_sums_in W^T + N b."""
@@ -238,34 +257,14 @@ def colsum_linear(col_sums_in: torch.Tensor, weight: torch.Tensor, bias: Optiona
     return out
 
 
+@_device_guard
 def lis_select_presummed(h, col_sums, wq, bq, wk, bk, k: int, logical_to_physical=None, physical_to_logical=None):
     """lis_select / lis_select_permuted with the column sums of the tokens supplied by their producer (fp32 [B, D] or [D]):
     the first HBM sweep over h is skipped.  h [N,D] or [B,N,D]."""
-    dev = _dev(h, col_sums, wq, bq, wk, bk, logical_to_physical, physical_to_logical)
-    b, n, d = _as_bnd(h)
-    if col_sums.dtype != torch.float32 or col_sums.numel() != b * d or not col_sums.is_contiguous():
-        raise ValueError("col_sums must be contiguous float32 with one row of D sums per segment")
-    if (logical_to_physical is None) != (physical_to_logical is None):
-        raise ValueError("give both permutation maps or neither")
-    if logical_to_physical is not None:
-        if logical_to_physical.dtype != torch.int64 or physical_to_logical.dtype != torch.int64:
-            raise TypeError("permutation maps must be int64")
-        if logical_to_physical.numel() != b * n or physical_to_logical.numel() != b * n:
-            raise ValueError("permutation maps must have one entry per token row")
-    sc = _scorer(wq, bq, wk, bk)
-    seg = _uniform_segments(b, n, int(k))
-    lib = N.lib()
-    ws = _workspace(lib.vsel_lis_workspace_bytes(C.byref(seg), d, sc.hd), dev)
-    lead = h.shape[:-2]
-    out = torch.empty(*lead, k, d, dtype=h.dtype, device=dev)
-    idx = torch.empty(*lead, k, dtype=torch.int64, device=dev)
-    scores = torch.empty(*lead, n, dtype=torch.float32, device=dev)
-    N.check(lib.vsel_lis_select_presummed(_stream(), h.data_ptr(), _code(h), C.byref(seg), C.byref(sc), col_sums.data_ptr(),
-                                          ws.data_ptr(), ws.numel(), _p(logical_to_physical), _p(physical_to_logical),
-                                          out.data_ptr(), idx.data_ptr(), scores.data_ptr()))
-    return out, idx, scores
+    return _lis_select_uniform("vsel_lis_select_presummed", h, wq, bq, wk, bk, k, logical_to_physical, physical_to_logical, col_sums)
 
 
+@_device_guard
 def lis_select_varlen(h, seg_lens: Sequence[int], ks: Sequence[int], wq, bq, wk, bk):
     """Ragged form: h [T,D] holds len(seg_lens) segments back to back; segment s keeps ks[s] rows.
     -> (out [sum ks, D], idx int64 [sum ks] local to the segment, scores fp32 [T])."""
@@ -292,6 +291,7 @@ def lis_select_varlen(h, seg_lens: Sequence[int], ks: Sequence[int], wq, bq, wk,
     return out, idx, scores
 
 
+@_device_guard
 def hard_topk(scores: torch.Tensor, k: int, want_mask: bool = False):
     """scores fp32 [B,N] or [N] -> idx int64 [B,k] ascending (topk(k).indices.sort()); optional 0/1 mask."""
     dev = _dev(scores)
@@ -306,6 +306,7 @@ def hard_topk(scores: torch.Tensor, k: int, want_mask: bool = False):
     return (idx, mask) if want_mask else idx
 
 
+@_device_guard
 def gather_rows(h: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """h [B,N,D] / [N,D], idx int64 [B,k] / [k] -> h[idx] per segment."""
     dev = _dev(h, idx)
@@ -321,6 +322,7 @@ def gather_rows(h: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 # differentiable top-k
 # ------------------------------------------------------------------------------------------------
 
+@_device_guard
 def soft_topk_fwd(xs: torch.Tensor, k: int, bf16_reference: bool = False):
     """_find_ts: (ps [B, N], ts [B]).  bf16_reference: the reference's own bfloat16 arithmetic (every step rounded to bf16: its
     bisection stalls on a bf16 neighbour of the root) instead of the fp32 root -- vsel_soft_topk_fwd_bf16ref, include/vsel.h."""
@@ -335,6 +337,7 @@ def soft_topk_fwd(xs: torch.Tensor, k: int, bf16_reference: bool = False):
     return ps, ts
 
 
+@_device_guard
 def soft_topk_bwd(grad_ps: torch.Tensor, xs: torch.Tensor, ts: torch.Tensor) -> torch.Tensor:
     _dev(grad_ps, xs, ts)
     b, n = xs.shape
@@ -347,6 +350,7 @@ def soft_topk_bwd(grad_ps: torch.Tensor, xs: torch.Tensor, ts: torch.Tensor) -> 
 # training block
 # ------------------------------------------------------------------------------------------------
 
+@_device_guard
 def lis_train_fwd(h, wq, bq, wk, bk, k: int):
     """One segment h [N,D] -> (h_new [N,D], ps [N], y [N], scores [N], ts [1], bce [1])."""
     dev = _dev(h, wq, bq, wk, bk)
@@ -363,6 +367,7 @@ def lis_train_fwd(h, wq, bq, wk, bk, k: int):
     return h_new, ps, y, scores, ts, bce
 
 
+@_device_guard
 def lis_train_bwd(d_hnew, h, wq, bq, wk, bk, ps, y, scores, ts, d_ps_ext=None, dl_dbce: float = 0.0, need_dh: bool = False,
                   out=None):
     """-> (dwq, dbq, dwk, dbk fp32, dh or None).  out = (dwq, dbq, dwk, dbk): contiguous fp32 buffers to OVERWRITE (e.g. the
@@ -388,6 +393,7 @@ def lis_train_bwd(d_hnew, h, wq, bq, wk, bk, ps, y, scores, ts, d_ps_ext=None, d
     return dwq, dbq, dwk, dbk, dh
 
 
+@_device_guard
 def lis_train_bwd_factors(d_hnew, h, wq, bq, wk, bk, ps, y, scores, ts, d_ps_ext=None, dl_dbce: float = 0.0,
                           need_dh: bool = False, out=None):
     """The same backward with the weight gradients as rank-1 factors: -> (payload fp32 [2 (Hd + D) + 2 Hd], dh or None),
@@ -413,6 +419,7 @@ def lis_train_bwd_factors(d_hnew, h, wq, bq, wk, bk, ps, y, scores, ts, d_ps_ext
     return out, dh
 
 
+@_device_guard
 def factors_to_grads(payload: torch.Tensor, hd: int, d: int, scale: float = 1.0, out=None):
     """payload fp32 [R, 2 (Hd + D) + 2 Hd] (rows of lis_train_bwd_factors, own and / or all-gathered) ->
     (dwq [Hd, D], dbq [Hd], dwk [Hd, D], dbk [Hd]) = scale x the sums over the rows, in row order."""
@@ -432,6 +439,7 @@ def factor_payload_split(payload: torch.Tensor, hd: int, d: int):
     return torch.split(payload, [hd, d, hd, d, hd, hd], dim=-1)
 
 
+@_device_guard
 def lis_scores_bwd(g, h, wq, bq, wk, bk, need_dh: bool = False):
     """Backward of lis_scores for one segment: g fp32 [N], h [N,D] -> (dwq, dbq, dwk, dbk fp32, dh or None)."""
     dev = _dev(g, h, wq, bq, wk, bk)
@@ -451,6 +459,7 @@ def lis_scores_bwd(g, h, wq, bq, wk, bk, need_dh: bool = False):
 # sequence splice
 # ------------------------------------------------------------------------------------------------
 
+@_device_guard
 def splice(input_ids, inputs_embeds, visual_token_id: int, all_indices, visual_embeds, n_visual: int,
            position_ids=None, attention_mask=None, check: bool = False):
     """Batch-1 splice on device.  input_ids [1, L] int64, inputs_embeds [1, L, D], all_indices [k] int64 ascending,
@@ -497,6 +506,7 @@ def splice(input_ids, inputs_embeds, visual_token_id: int, all_indices, visual_e
     return sel, new_ids, new_emb, new_pos, new_am
 
 
+@_device_guard
 def splice_batched(input_ids, inputs_embeds, visual_token_id: int, seq_lens: Sequence[int], visual_lens: Sequence[int],
                    ks: Sequence[int], all_indices, visual_embeds, position_ids=None, check: bool = False):
     """Packed-batch splice.  input_ids [T] int64 = S prompts back to back (seq_lens), prompt s holding visual_lens[s]
@@ -526,13 +536,7 @@ def splice_batched(input_ids, inputs_embeds, visual_token_id: int, seq_lens: Seq
     d = inputs_embeds.shape[-1]
     l_out = t - n_tot + k_tot
 
-    def _cu(lens):
-        c = [0]
-        for x in lens:
-            c.append(c[-1] + int(x))
-        return torch.tensor(c, dtype=torch.int32).to(dev, non_blocking=True)
-
-    cu_s, cu_v, cu_k = _cu(seq_lens), _cu(visual_lens), _cu(ks)
+    cu_s, cu_v, cu_k = _cu_int32(seq_lens, dev), _cu_int32(visual_lens, dev), _cu_int32(ks, dev)
     vis = visual_embeds.to(inputs_embeds.dtype).contiguous()
     emb = inputs_embeds.contiguous()
     pos = None
@@ -580,10 +584,7 @@ def _select_splice_common(h, input_ids, inputs_embeds, seq_lens, visual_lens, ks
         seg, cu_r, cu_o, cu_s = _uniform_segments(1, int(visual_lens[0]), int(ks[0])), None, None, None
     else:
         seg, cu_r, cu_o = _ragged_segments(visual_lens, ks, dev)
-        c = [0]
-        for x in seq_lens:
-            c.append(c[-1] + int(x))
-        cu_s = torch.tensor(c, dtype=torch.int32).to(dev, non_blocking=True)
+        cu_s = _cu_int32(seq_lens, dev)
     n_tot, k_tot = sum(visual_lens), sum(ks)
     l_out = t - n_tot + k_tot
     d = h.shape[1]
@@ -603,17 +604,6 @@ def _select_splice_common(h, input_ids, inputs_embeds, seq_lens, visual_lens, ks
     return seg, (cu_r, cu_o), cu_s, pos, rows, am, out, l_out, max_len_out, n_tot, k_tot
 
 
-def _row_map(m, name: str, rows: int):
-    """A row permutation map as the C-ABI reads it: int64, contiguous, one entry per token row (or None)."""
-    if m is None:
-        return None
-    if m.dtype != torch.int64:
-        raise TypeError(f"{name} must be int64 (got {m.dtype})")
-    if m.numel() != rows:
-        raise ValueError(f"{name} must have one entry per token row ({rows}), got {m.numel()}")
-    return m.contiguous()
-
-
 def _select_splice_finish(o, check, n_tot, l_out, k_tot, attention_mask):
     if check:
         found, written, kept, bad = o["stats"].tolist()
@@ -625,6 +615,7 @@ def _select_splice_finish(o, check, n_tot, l_out, k_tot, attention_mask):
     return new_am
 
 
+@_device_guard
 def lis_select_splice(h, wq, bq, wk, bk, input_ids, inputs_embeds, visual_token_id: int, seq_lens: Sequence[int],
                       visual_lens: Sequence[int], ks: Sequence[int], position_ids=None, attention_mask=None, col_sums=None,
                       logical_to_physical=None, physical_to_logical=None, check: bool = False, soft: bool = False):
@@ -675,6 +666,7 @@ def lis_select_splice(h, wq, bq, wk, bk, input_ids, inputs_embeds, visual_token_
                 position_ids=o["new_pos"], attention_mask=new_am, cu_seqlens=o["cu_out"], soft_ps=soft_ps, soft_ts=soft_ts)
 
 
+@_device_guard
 def topk_select_splice(scores, h, input_ids, inputs_embeds, visual_token_id: int, seq_lens: Sequence[int],
                        visual_lens: Sequence[int], ks: Sequence[int], position_ids=None, attention_mask=None,
                        logical_to_physical=None, check: bool = False):
@@ -700,6 +692,16 @@ def topk_select_splice(scores, h, input_ids, inputs_embeds, visual_token_id: int
 # var-len attention
 # ------------------------------------------------------------------------------------------------
 
+def _qkv_bf16(name: str, *ts: torch.Tensor, what: str = "q/k/v") -> None:
+    if any(t.dtype != torch.bfloat16 for t in ts):
+        raise TypeError(f"{name} takes bfloat16 {what}")
+
+
+def _scale(softmax_scale: Optional[float], d: int) -> float:
+    return float(softmax_scale) if softmax_scale is not None else d ** -0.5
+
+
+@_device_guard
 def varlen_attn(q, k, v, cu_seqlens: torch.Tensor, max_seqlen: int, causal: bool = True,
                 softmax_scale: Optional[float] = None, key_parts: bool = False) -> torch.Tensor:
     """q [T,Hq,d], k/v [T,Hkv,d] bf16, cu_seqlens int32 [S+1] on device -> out [T,Hq,d].
@@ -707,13 +709,12 @@ def varlen_attn(q, k, v, cu_seqlens: torch.Tensor, max_seqlen: int, causal: bool
     (vsel_varlen_attn_fwd_ws) -- opt-in, because that form sums in another fp32 order than the others (a prompt's result would otherwise
     depend on what it is packed with) and ignores cu_seqlens beyond their count: the equal-length layout is checked here."""
     dev = _dev(q, k, v, cu_seqlens)
-    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
-        raise TypeError("varlen_attn takes bfloat16 q/k/v")
+    _qkv_bf16("varlen_attn", q, k, v)
     if cu_seqlens.dtype != torch.int32:
         raise TypeError("cu_seqlens must be int32")
     t, hq, d = q.shape
     hkv = k.shape[1]
-    scale = float(softmax_scale) if softmax_scale is not None else d ** -0.5
+    scale = _scale(softmax_scale, d)
     out = torch.empty_like(q)
     lib = N.lib()
     n_seq = cu_seqlens.numel() - 1
@@ -732,17 +733,17 @@ def varlen_attn(q, k, v, cu_seqlens: torch.Tensor, max_seqlen: int, causal: bool
     return out
 
 
+@_device_guard
 def varlen_attn_fwd_lse(q, k, v, cu_seqlens: torch.Tensor, max_seqlen: int, causal: bool = True,
                         softmax_scale: Optional[float] = None):
     """varlen_attn that also returns lse fp32 [T, Hq] (log-sum-exp of the scaled visible scores) for varlen_attn_bwd."""
     dev = _dev(q, k, v, cu_seqlens)
-    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
-        raise TypeError("varlen_attn takes bfloat16 q/k/v")
+    _qkv_bf16("varlen_attn", q, k, v)
     if cu_seqlens.dtype != torch.int32:
         raise TypeError("cu_seqlens must be int32")
     t, hq, d = q.shape
     hkv = k.shape[1]
-    scale = float(softmax_scale) if softmax_scale is not None else d ** -0.5
+    scale = _scale(softmax_scale, d)
     out = torch.empty_like(q)
     lse = torch.empty(t, hq, dtype=torch.float32, device=dev)
     N.check(N.lib().vsel_varlen_attn_fwd_lse(_stream(), q.data_ptr(), k.data_ptr(), v.data_ptr(), cu_seqlens.data_ptr(),
@@ -751,13 +752,13 @@ def varlen_attn_fwd_lse(q, k, v, cu_seqlens: torch.Tensor, max_seqlen: int, caus
     return out, lse
 
 
+@_device_guard
 def varlen_attn_bwd(dout, q, k, v, out, lse, cu_seqlens: torch.Tensor, max_seqlen: int, causal: bool = True,
                     softmax_scale: Optional[float] = None):
     """Backward of varlen_attn: dout/out/q [T,Hq,d], k/v [T,Hkv,d] bf16 contiguous, lse fp32 [T,Hq] -> (dq, dk, dv) bf16."""
     dev = _dev(dout, q, k, v, out, lse, cu_seqlens)
     for x in (dout, q, k, v, out):
-        if x.dtype != torch.bfloat16:
-            raise TypeError("varlen_attn_bwd takes bfloat16 tensors")
+        _qkv_bf16("varlen_attn_bwd", x, what="tensors")
         if not x.is_contiguous():
             raise ValueError("varlen_attn_bwd takes contiguous tensors")
     if lse.dtype != torch.float32 or cu_seqlens.dtype != torch.int32:
@@ -766,7 +767,7 @@ def varlen_attn_bwd(dout, q, k, v, out, lse, cu_seqlens: torch.Tensor, max_seqle
     hkv = k.shape[1]
     if dout.shape != q.shape or out.shape != q.shape or v.shape != k.shape or lse.shape != (t, hq):
         raise ValueError("varlen_attn_bwd: shape mismatch")
-    scale = float(softmax_scale) if softmax_scale is not None else d ** -0.5
+    scale = _scale(softmax_scale, d)
     lib = N.lib()
     ws = _workspace(lib.vsel_varlen_attn_bwd_workspace_bytes(t, hq, hkv, cu_seqlens.numel() - 1, int(max_seqlen)), dev)
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
@@ -776,18 +777,18 @@ def varlen_attn_bwd(dout, q, k, v, out, lse, cu_seqlens: torch.Tensor, max_seqle
     return dq, dk, dv
 
 
+@_device_guard
 def varlen_attn_kv(q, k, v, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor, max_seqlen_q: int, causal: bool = True,
                    softmax_scale: Optional[float] = None) -> torch.Tensor:
     """Separate query / key packings: q [Tq,Hq,d], k/v [Tk,Hkv,d] bf16, cu_seqlens_q / cu_seqlens_k int32 [S+1] ->
     out [Tq,Hq,d].  Bottom-right aligned causal mask (query i of a sequence sees keys <= i + klen - qlen)."""
     dev = _dev(q, k, v, cu_seqlens_q, cu_seqlens_k)
-    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
-        raise TypeError("varlen_attn_kv takes bfloat16 q/k/v")
+    _qkv_bf16("varlen_attn_kv", q, k, v)
     if cu_seqlens_q.dtype != torch.int32 or cu_seqlens_k.dtype != torch.int32 or cu_seqlens_q.numel() != cu_seqlens_k.numel():
         raise TypeError("cu_seqlens_q / cu_seqlens_k must be int32 of the same length")
     tq, hq, d = q.shape
     hkv = k.shape[1]
-    scale = float(softmax_scale) if softmax_scale is not None else d ** -0.5
+    scale = _scale(softmax_scale, d)
     seqlens_k = (cu_seqlens_k[1:] - cu_seqlens_k[:-1]).contiguous()
     out = torch.empty_like(q)
     N.check(N.lib().vsel_varlen_attn_fwd_kv(_stream(), q.data_ptr(), k.data_ptr(), v.data_ptr(), cu_seqlens_q.data_ptr(),
@@ -807,18 +808,18 @@ def head_major_ok(t: torch.Tensor) -> bool:
             and t.data_ptr() % 16 == 0)
 
 
+@_device_guard
 def attn_head_major(query, key, value, causal: bool = True, softmax_scale: Optional[float] = None) -> torch.Tensor:
     """HuggingFace layout without copies: query [B, Hq, Lq, d], key / value [B, Hkv, Lk, d] bf16, either contiguous in that
     layout or a transposed view of a packed [B, L, H, d] tensor (what HF hands over for v) -> out [B, Lq, Hq, d].  Every batch
     row is one sequence; Lq < Lk: bottom-right aligned causal mask (decode / chunked prefill against the cache)."""
     dev = _dev(query, key, value, strided_ok=True)            # strides are validated by head_major_ok below
-    if query.dtype != torch.bfloat16 or key.dtype != torch.bfloat16 or value.dtype != torch.bfloat16:
-        raise TypeError("attn_head_major takes bfloat16 tensors")
+    _qkv_bf16("attn_head_major", query, key, value, what="tensors")
     b, hq, lq, d = query.shape
     hkv, lk = key.shape[1], key.shape[2]
     if value.shape != key.shape or not all(head_major_ok(t) for t in (query, key, value)):
         raise ValueError("attn_head_major takes [B, H, L, d] tensors with unit feature stride and a dense batch stride")
-    scale = float(softmax_scale) if softmax_scale is not None else d ** -0.5
+    scale = _scale(softmax_scale, d)
     # the index tensors are the same for every layer of a forward: build them once per (B, Lq, Lk, device)
     key_ = (b, lq, lk, dev)
     if _head_major_meta.get("key") != key_:
@@ -837,13 +838,13 @@ def attn_head_major(query, key, value, causal: bool = True, softmax_scale: Optio
     return out
 
 
+@_device_guard
 def paged_attn(q, k_cache, v_cache, cu_seqlens_q: torch.Tensor, seqlens_k: torch.Tensor, block_table: torch.Tensor,
                max_seqlen_q: int, causal: bool = True, softmax_scale: Optional[float] = None) -> torch.Tensor:
     """q [Tq,Hq,d] bf16; k_cache / v_cache [n_pages, page_size, Hkv, d] bf16; cu_seqlens_q int32 [S+1];
     seqlens_k int32 [S]; block_table int32 [S, max_pages] -> out [Tq,Hq,d].  Bottom-right aligned causal mask."""
     dev = _dev(q, k_cache, v_cache, cu_seqlens_q, seqlens_k, block_table)
-    if q.dtype != torch.bfloat16 or k_cache.dtype != torch.bfloat16 or v_cache.dtype != torch.bfloat16:
-        raise TypeError("paged_attn takes bfloat16 q / k_cache / v_cache")
+    _qkv_bf16("paged_attn", q, k_cache, v_cache, what="q / k_cache / v_cache")
     for t in (cu_seqlens_q, seqlens_k, block_table):
         if t.dtype != torch.int32:
             raise TypeError("cu_seqlens_q / seqlens_k / block_table must be int32")
@@ -852,7 +853,7 @@ def paged_attn(q, k_cache, v_cache, cu_seqlens_q: torch.Tensor, seqlens_k: torch
     n_seq = seqlens_k.numel()
     if block_table.dim() != 2 or block_table.shape[0] != n_seq or cu_seqlens_q.numel() != n_seq + 1:
         raise ValueError("block_table must be [n_seq, max_pages] and cu_seqlens_q [n_seq + 1]")
-    scale = float(softmax_scale) if softmax_scale is not None else d ** -0.5
+    scale = _scale(softmax_scale, d)
     out = torch.empty_like(q)
     N.check(N.lib().vsel_paged_attn_fwd(_stream(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), cu_seqlens_q.data_ptr(),
                                         seqlens_k.data_ptr(), block_table.data_ptr(), block_table.shape[1], page_size, n_seq,
@@ -868,6 +869,7 @@ def _strides3(t: torch.Tensor, name: str):
     return t.stride(0), t.stride(1), t.stride(2)
 
 
+@_device_guard
 def kvcache_attn(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None, cache_batch_idx=None,
                  cache_leftpad=None, block_table=None, softmax_scale: Optional[float] = None, causal: bool = False,
                  rotary_interleaved: bool = True, return_softmax_lse: bool = False, out: Optional[torch.Tensor] = None):
@@ -923,7 +925,7 @@ def kvcache_attn(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_si
             raise ValueError("rotary_cos / rotary_sin must be two [seqlen_ro, rotary_dim / 2] tables of one dtype")
         if rotary_cos.dtype not in (torch.bfloat16, torch.float32):
             raise TypeError("rotary tables must be bfloat16 or float32")
-    scale = float(softmax_scale) if softmax_scale is not None else d ** -0.5
+    scale = _scale(softmax_scale, d)
     lib = N.lib()
     if q is not None and out is None:
         out = torch.empty(b, s_q, hq, d, dtype=torch.bfloat16, device=dev)
@@ -953,6 +955,7 @@ def check_sampling_args(temperature, top_p, top_k, seed) -> Tuple[float, float, 
     return t, p, _int_in("top_k", top_k, 0), _int_in("seed", seed, 0, 2 ** 64)
 
 
+@_device_guard
 def sample_tokens(logits: torch.Tensor, temperature: float, top_p: float = 1.0, top_k: int = 0, seed: int = 0,
                   row_ids: Optional[torch.Tensor] = None, step: int = 0, return_kept: bool = False):
     """vsel_sample_tokens: one token per row of logits [B, V] (bf16 / fp32, any row stride, contiguous columns) by temperature,
@@ -988,6 +991,7 @@ def check_row_sampling_args(temperature=1.0, top_p=1.0, top_k=0, min_p=0.0) -> T
     return t, p, _int_in("top_k", top_k, 0, 2 ** 31), mp
 
 
+@_device_guard
 def sample_tokens_rows(logits: torch.Tensor, temperature=None, top_p=None, top_k=None, min_p=None, seed: int = 0,
                        row_ids: Optional[torch.Tensor] = None, step: int = 0, return_kept: bool = False, return_logprobs: bool = False):
     """vsel_sample_tokens_rows: sample_tokens with each row's own parameters ("per-row parameters").  temperature, top_p,
@@ -1040,6 +1044,7 @@ def check_repetition_penalty(penalty) -> float:
     return p
 
 
+@_device_guard
 def token_sets(ids_list, vocab: int, device) -> torch.Tensor:
     """vsel_token_sets_build: one bitset of ceil(vocab / 32) uint32 words (held as int32) per entry of ids_list (1-D int tensors on any
     device, or int sequences; duplicates count once) -> int32 [len(ids_list), ceil(vocab / 32)] on `device`, for repetition_penalty.
@@ -1070,6 +1075,7 @@ def token_sets(ids_list, vocab: int, device) -> torch.Tensor:
     return sets
 
 
+@_device_guard
 def repetition_penalty(logits: torch.Tensor, penalty: float, sets: torch.Tensor, row_ids: Optional[torch.Tensor] = None,
                        prev_tokens: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, return_tokens: bool = False):
     """vsel_repetition_penalty: HF's RepetitionPenaltyLogitsProcessor on logits [B, V] (bf16 / fp32, any row stride, contiguous columns)
@@ -1098,6 +1104,7 @@ def repetition_penalty(logits: torch.Tensor, penalty: float, sets: torch.Tensor,
     return tokens if out is None else (out, tokens)
 
 
+@_device_guard
 def decode_advance(next_tokens: torch.Tensor, eos: Optional[torch.Tensor], max_new_tokens: int, done: torch.Tensor, n_tokens: torch.Tensor,
                    cache_seqlens: torch.Tensor, pos: torch.Tensor, feed: torch.Tensor, tokens_out: torch.Tensor, status: torch.Tensor) -> None:
     """vsel_decode_advance: the bookkeeping of one decode step, on the device.  next_tokens int64 [B] from the step's
@@ -1133,6 +1140,7 @@ def _logprob_args(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int
     return dev, code, rows, v, stride, _int_in("ignore_index", ignore_index, -2 ** 63, 2 ** 63)
 
 
+@_device_guard
 def token_logprob_fwd(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100, reduce: bool = False):
     """vsel_token_logprob_fwd without autograd: logits [rows, V] (bf16 / fp32, any row stride, contiguous columns), targets int64 [rows]
     -> logprob fp32 [rows] (x_t - lse; 0 for a row whose target is ignore_index, NaN for a target outside [0, V)) and lse fp32 [rows];
@@ -1150,6 +1158,7 @@ def token_logprob_fwd(logits: torch.Tensor, targets: torch.Tensor, ignore_index:
     return (logprob, lse, total, n_valid) if reduce else (logprob, lse)
 
 
+@_device_guard
 def token_logprob_bwd(logits: torch.Tensor, targets: torch.Tensor, lse: torch.Tensor, grad_rows: Optional[torch.Tensor] = None,
                       grad_scale: Optional[torch.Tensor] = None, ignore_index: int = -100) -> torch.Tensor:
     """vsel_token_logprob_bwd: grad_logits [rows, V] contiguous in logits' dtype, row r = c_r ([j == t] - exp(x_j - lse[r])) with
@@ -1188,6 +1197,7 @@ class _TokenLogprobs(torch.autograd.Function):
         return token_logprob_bwd(logits, targets, lse, grad_rows=g, ignore_index=ctx.ignore_index), None, None
 
 
+@_device_guard
 def token_logprobs(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100):
     """Per-token log-probabilities of given tokens: logits [rows, V] (bf16 / fp32, any row stride, contiguous columns), targets int64
     [rows] -> (logprob fp32 [rows], lse fp32 [rows]); see token_logprob_fwd.  Differentiable in logits (the gradient comes from
@@ -1195,12 +1205,3 @@ def token_logprobs(logits: torch.Tensor, targets: torch.Tensor, ignore_index: in
     a gradient that reaches it raises in the backward."""
     _logprob_args(logits, targets, ignore_index)
     return _TokenLogprobs.apply(logits, targets, ignore_index)
-
-
-# every op that reaches libvsel switches to its tensors' device first
-for _name in ("token_logprob_fwd", "token_logprob_bwd", "token_logprobs","lis_scores", "lis_select", "lis_select_permuted", "gelu_colsum", "colsum_linear", "lis_select_presummed", "lis_select_varlen",
-              "hard_topk", "gather_rows", "soft_topk_fwd", "soft_topk_bwd", "lis_train_fwd", "lis_train_bwd", "lis_train_bwd_factors", "factors_to_grads", "lis_scores_bwd",
-              "splice", "splice_batched", "lis_select_splice", "topk_select_splice", "varlen_attn", "varlen_attn_fwd_lse", "varlen_attn_bwd", "varlen_attn_kv",
-              "attn_head_major", "paged_attn", "kvcache_attn", "sample_tokens", "sample_tokens_rows", "token_sets", "repetition_penalty", "decode_advance"):
-    globals()[_name] = _device_guard(globals()[_name])
-del _name
