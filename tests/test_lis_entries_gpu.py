@@ -1,6 +1,6 @@
 """Every entry that runs the LIS scores stage gives the same scores, bit for bit, on the same tokens: lis_scores, lis_select,
 lis_select_varlen, lis_select_permuted, lis_select_splice and (one segment) lis_train_fwd -- on both sides of the bf16x3-MFMA
-condition of make_plan (csrc/lis_kernels.h: D % 16 == 0 and Hd % 16 == 0), for every (token, weight) dtype pair check_scorer
+condition of make_plan (csrc/lis_stages.h: D % 16 == 0 and Hd % 16 == 0), for every (token, weight) dtype pair check_scorer
 accepts, for a batch the small-batch form takes (1) and one it never takes (9 > kSmallMaxSeg), with the small-batch form on
 (default) and off (knob lis_small_path = 0).  Run on the MI355X box:  pytest -m gpu."""
 import pytest

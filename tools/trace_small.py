@@ -5,7 +5,8 @@
     python tools/trace_small.py [B]        # on the GPU box: run, read the stamps of the last call, print the timeline
 
 -DVSEL_TRACE makes thread 0 of every workgroup leave s_memrealtime stamps (100 MHz, device-wide clock) at the phase edges of
-the five kernels (csrc/lis_kernels.h VSEL_STAMP).  The shipped libvsel.so is built without it.
+the five kernels (csrc/lis_kernels.h, lis_small.h VSEL_STAMP; all compiled in lis.hip, whose table vsel_debug_read_trace reads).  The
+shipped libvsel.so is built without it.
 """
 import ctypes as C
 import glob

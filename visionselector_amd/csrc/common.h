@@ -21,7 +21,8 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 struct bf16_t { uint16_t bits; };
 
 // -DVSEL_TRACE (tools/trace_small.py / tools/trace_attn.py build with it; never in the shipped library): thread 0 of every
-// workgroup leaves s_memrealtime stamps (100 MHz, one clock for the whole device) at phase edges.  One table per translation unit.
+// workgroup leaves s_memrealtime stamps (100 MHz, one clock for the whole device) at phase edges.  One table per translation unit
+// (every stamped LIS kernel is compiled in lis.hip, whose table vsel_debug_read_trace copies out).
 #ifdef VSEL_TRACE
 constexpr int kTraceKernels = 8, kTraceBlocks = 1024, kTraceSlots = 8;
 static __device__ unsigned long long g_trace[kTraceKernels][kTraceBlocks][kTraceSlots];
@@ -127,15 +128,22 @@ __device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {
   return u >> 16;
 }
 
-// load kVec consecutive elements (16 B, must be 16-B aligned) and widen to fp32
-__device__ __forceinline__ void load_vec(const bf16_t* p, float (&v)[8]) {
-  const u32x4 r = *reinterpret_cast<const u32x4*>(p);
+// a raw 16-byte vector of T (kept raw until it is consumed, so that no wait is forced at the load) widened to fp32
+template <typename T> __device__ __forceinline__ void unpack_vec(u32x4 raw, float (&v)[Elem<T>::kVec]);
+template <> __device__ __forceinline__ void unpack_vec<bf16_t>(u32x4 raw, float (&v)[8]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(r[i] << 16);
-    v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u);
+    v[2 * i] = __uint_as_float(raw[i] << 16);
+    v[2 * i + 1] = __uint_as_float(raw[i] & 0xffff0000u);
   }
 }
+template <> __device__ __forceinline__ void unpack_vec<float>(u32x4 raw, float (&v)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] = __uint_as_float(raw[i]);
+}
+
+// load kVec consecutive elements (16 B, must be 16-B aligned) and widen to fp32
+__device__ __forceinline__ void load_vec(const bf16_t* p, float (&v)[8]) { unpack_vec<bf16_t>(*reinterpret_cast<const u32x4*>(p), v); }
 __device__ __forceinline__ void load_vec(const float* p, float (&v)[4]) {
   const f32x4 r = *reinterpret_cast<const f32x4*>(p);
 #pragma unroll
@@ -143,12 +151,7 @@ __device__ __forceinline__ void load_vec(const float* p, float (&v)[4]) {
 }
 // streaming variants: the token tensor is far larger than the caches and each sweep reads a byte once -> non-temporal loads
 __device__ __forceinline__ void load_vec_stream(const bf16_t* p, float (&v)[8]) {
-  const u32x4 r = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(r[i] << 16);
-    v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u);
-  }
+  unpack_vec<bf16_t>(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)), v);
 }
 __device__ __forceinline__ void load_vec_stream(const float* p, float (&v)[4]) {
   const f32x4 r = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
@@ -171,6 +174,29 @@ __device__ __forceinline__ float load_elem(const bf16_t* p) { return bf16_to_f32
 __device__ __forceinline__ float load_elem(const float* p) { return *p; }
 __device__ __forceinline__ void store_elem(bf16_t* p, float v) { p->bits = (uint16_t)f32_to_bf16_bits(v); }
 __device__ __forceinline__ void store_elem(float* p, float v) { *p = v; }
+
+// sum_{j<n} p[j * stride] in index order.  24 loads in flight per batch, UNCONDITIONAL with a clamped index (a plain loop
+// serialises on latency; an 8-wide batch plus a scalar tail made 18 partials four round trips, 14 slabs seven)
+__device__ __forceinline__ float strided_sum(const float* __restrict__ p, int n, int64_t stride) {
+  float acc = 0.f;
+  for (int j = 0; j < n; j += 24) {
+    float v[24];
+#pragma unroll
+    for (int u = 0; u < 24; ++u) v[u] = p[(int64_t)min(j + u, n - 1) * stride];
+#pragma unroll
+    for (int u = 0; u < 24; ++u)
+      if (j + u < n) acc += v[u];
+  }
+  return acc;
+}
+
+// key of the hard top-k's radix select: unsigned order = the scores' order
+__device__ __forceinline__ uint32_t order_key(float x) {
+  const float f = x + 0.0f;  // -0.0 -> +0.0
+  const uint32_t u = __float_as_uint(f);
+  if (f != f) return 0xffffffffu;  // NaN sorts greatest (torch.topk convention)
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
 
 // ---- wave64 reductions (fixed order => deterministic) -----------------------------------------
 // DPP instead of __shfl_xor: hipcc lowers every __shfl_xor to ds_bpermute_b32 (an LDS-crossbar round trip, ~6 dependent

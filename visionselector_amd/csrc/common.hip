@@ -31,7 +31,7 @@ namespace vsel {
 namespace {
 struct KnobSpec { const char* env; int def, lo, hi; };
 constexpr KnobSpec kKnobs[VSEL_KNOB_COUNT] = {
-    {"VSEL_SMALL_PATH", 4, 0, 8},      // VSEL_KNOB_LIS_SMALL_PATH (8 = lis_small.h's kSmallMaxSeg)
+    {"VSEL_SMALL_PATH", 4, 0, 8},      // VSEL_KNOB_LIS_SMALL_PATH (8 = lis_stages.h's kSmallMaxSeg)
     {"VSEL_FUSED_SELECT", 48, 0, 1 << 30},
     {nullptr, 0, 0, 8},                // VSEL_KNOB_ATTN_WAVES
     {nullptr, 2, 0, 2},                // VSEL_KNOB_ATTN_PACK

@@ -7,8 +7,7 @@
 // This kernel replaces the GELU launch: it writes G exactly as nn.GELU() would (erf form, fp32 math, rounded to the
 // activation dtype) and accumulates the column sums of the ROUNDED G on the way -- no extra HBM traffic -- so that
 // vsel_lis_select_presummed can skip sweep 1.  Deterministic: fixed row chunks per workgroup, then a fixed-order finish.
-#include "common.h"
-#include "lis_kernels.h"
+#include "lis_stages.h"
 
 namespace vsel {
 
@@ -148,7 +147,7 @@ static __global__ __launch_bounds__(1024) void gelu_colsum_finish_kernel(const f
 // on the STORED (bf16) weight with fp32 accumulation -- torch's route was weight.float().t() (a 73 MB fp32 copy per call at 7B)
 // + an fp32 addmm.  Few segments: one wave per output row, the weight row (Cin x 2 B, contiguous) read once with every load of
 // a batch in flight, fp32 FMA against the <= kLinSmallSeg input rows, fixed-order lane reduction.  Many segments: the scorer's
-// own bf16x3 MFMA projection (proj_bf16x3.h: planes of in / N_s, gemm_nt, slabs) and a finish that adds the bias and scales
+// own bf16x3 MFMA projection (lis_stages.h: planes of in / N_s, gemm_nt, slabs) and a finish that adds the bias and scales
 // back by N_s.  Deterministic either way.
 // -------------------------------------------------------------------------------------------------------------------------
 constexpr int kLinSmallSeg = 8;
@@ -241,7 +240,7 @@ extern "C" size_t vsel_gelu_colsum_workspace_bytes(const vsel_segments* seg, int
 extern "C" int vsel_gelu_colsum(void* stream, const void* x, vsel_dtype dtype, const vsel_segments* seg, int64_t cols, void* y,
                                 float* col_sums, void* workspace, size_t workspace_bytes) {
   if (!x || !y || (col_sums && !workspace)) return fail(VSEL_ERR_INVALID, "NULL pointer");
-  int rc = check_segments_impl(seg, false);
+  int rc = check_segments(seg, false);
   if (rc) return rc;
   if (dtype != VSEL_BF16 && dtype != VSEL_F32) return fail(VSEL_ERR_INVALID, "bad dtype");
   const int vec = dtype == VSEL_BF16 ? 8 : 4;
@@ -286,7 +285,7 @@ extern "C" int vsel_colsum_linear(void* stream, const float* col_sums_in, const 
                                   const void* bias, vsel_dtype wdtype, int64_t cin, int64_t cout, float* col_sums_out,
                                   void* workspace, size_t workspace_bytes) {
   if (!col_sums_in || !weight || !col_sums_out) return fail(VSEL_ERR_INVALID, "NULL pointer");
-  int rc = check_segments_impl(seg, false);
+  int rc = check_segments(seg, false);
   if (rc) return rc;
   if (wdtype != VSEL_BF16 && wdtype != VSEL_F32) return fail(VSEL_ERR_INVALID, "bad dtype");
   const int vec = wdtype == VSEL_BF16 ? 8 : 4;
@@ -320,15 +319,10 @@ extern "C" int vsel_colsum_linear(void* stream, const float* col_sums_in, const 
   if ((uintptr_t)workspace & 15) return fail(VSEL_ERR_INVALID, "workspace must be 16-byte aligned");
   uint16_t* planes = (uint16_t*)((char*)workspace + p.off_planes);
   float* slabs = (float*)((char*)workspace + p.off_slabs);
-  const unsigned mtiles = (unsigned)(p.m_pad / 32);
   // planes of in[s][.] / N_s (row_splits = 1: the "partials" are the sums themselves); rows m >= S of a tile are never read back
-  VSEL_LAUNCH(colsum_finish_split_kernel, dim3((unsigned)cdiv(cin, 256), S), dim3(256), 0, st, col_sums_in, sv, (int)cin, 1, S,
-                     planes);
-  VSEL_AFTER_LAUNCH(st, "colsum_finish_split_kernel");
-  VSEL_LAUNCH(gemm_nt_bf16x3_kernel<kProjWaves>, dim3((unsigned)cdiv(cout, 64), (unsigned)cdiv(mtiles, kProjWaves), p.ks), dim3(64 * kProjWaves), 0, st, planes,
-                     (const uint16_t*)weight, S, (int)cout, (int)cin, p.kslice, slabs, (int)mtiles);
-  VSEL_AFTER_LAUNCH(st, "gemm_nt_bf16x3_kernel");
-  VSEL_LAUNCH(colsum_linear_finish_kernel, dim3(mtiles, (unsigned)cdiv(cout, 8)), dim3(256), 0, st, slabs, p.ks, S, (int)cout,
+  if ((rc = launch_colsum_finish_split(st, col_sums_in, sv, (int)cin, 1, S, planes))) return rc;
+  if ((rc = launch_gemm_nt_bf16x3(st, planes, (const uint16_t*)weight, S, (int)cout, (int)cin, p.kslice, p.ks, slabs))) return rc;
+  VSEL_LAUNCH(colsum_linear_finish_kernel, dim3(p.m_pad / 32, (unsigned)cdiv(cout, 8)), dim3(256), 0, st, slabs, p.ks, S, (int)cout,
                      p.m_pad, (const uint16_t*)bias, sv, col_sums_out);
   VSEL_AFTER_LAUNCH(st, "colsum_linear_finish_kernel");
   return VSEL_OK;

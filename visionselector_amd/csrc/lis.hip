@@ -1,12 +1,28 @@
-// C-ABI entry points of the LIS inference path (kernels in lis_kernels.h).
+// C-ABI entry points of the LIS inference path and the one file that compiles its kernels (lis_kernels.h, lis_small.h, proj_bf16x3.h,
+// with their launchers); the other files reach those through lis_stages.h.
+#define VSEL_LIS_KERNELS_TU
 #include "lis_kernels.h"
 #include "lis_small.h"
 
-#include <stdlib.h>
-
-namespace vsel {
-int check_segments(const vsel_segments* seg, bool need_k) { return check_segments_impl(seg, need_k); }
-}  // namespace vsel
+int vsel::check_segments(const vsel_segments* seg, bool need_k) {
+  if (!seg) return fail(VSEL_ERR_INVALID, "segments is NULL");
+  if (seg->n_seg < 1 || seg->rows_per_seg < 1 || seg->total_rows < 1)
+    return fail(VSEL_ERR_INVALID, "empty segments (n_seg=%lld rows_per_seg=%lld total_rows=%lld)", (long long)seg->n_seg, (long long)seg->rows_per_seg,
+                (long long)seg->total_rows);
+  if (seg->n_seg > 65535) return fail(VSEL_ERR_UNSUPPORTED, "n_seg %lld > 65535", (long long)seg->n_seg);
+  if (seg->total_rows >= (1ll << 31)) return fail(VSEL_ERR_UNSUPPORTED, "total_rows must fit int32");
+  if (!seg->seg_rows && seg->total_rows != seg->n_seg * seg->rows_per_seg)
+    return fail(VSEL_ERR_INVALID, "uniform segments: total_rows != n_seg * rows_per_seg");
+  if (need_k) {
+    if (seg->k < 1 || seg->k > seg->rows_per_seg)
+      return fail(VSEL_ERR_INVALID, "k=%lld must satisfy 1 <= k <= rows_per_seg=%lld", (long long)seg->k, (long long)seg->rows_per_seg);
+    if ((seg->seg_rows != nullptr) != (seg->seg_out != nullptr))
+      return fail(VSEL_ERR_INVALID, "seg_rows and seg_out must both be given (ragged) or both NULL (uniform)");
+    if (!seg->seg_out && seg->total_out != seg->n_seg * seg->k)
+      return fail(VSEL_ERR_INVALID, "uniform segments: total_out != n_seg * k");
+  }
+  return VSEL_OK;
+}
 
 using namespace vsel;
 
@@ -29,9 +45,19 @@ extern "C" int vsel_debug_read_trace(unsigned long long* out, int clear) {
 // 428.7 -> up to 48.  VSEL_FUSED_SELECT=<n> / knob VSEL_KNOB_LIS_FUSED_SELECT.
 static inline int fused_select_max_seg() { return knob(VSEL_KNOB_LIS_FUSED_SELECT); }
 
+// (here, not in lis_small.h beside its kernel: only the training backward calls it, and bench.py prices every launch those files name)
+int vsel::launch_proj_nt_small_pair(hipStream_t st, const float* partial0, const float* partial1, const SegView& sv, int S, int row_splits,
+                              const uint16_t* w0, const uint16_t* w1, int N, int K, int kslice, int ks, float* part0, float* part1,
+                              int64_t split_stride, int mean0, int mean1) {
+  VSEL_LAUNCH(proj_nt_small_pair_kernel, dim3((unsigned)cdiv(N, 32), ks, 2), dim3(64), 0, st, partial0, partial1, sv, S, row_splits, w0, w1, N,
+              K, kslice, part0, part1, split_stride, mean0, mean1);
+  VSEL_AFTER_LAUNCH(st, "proj_nt_small_pair_kernel");
+  return VSEL_OK;
+}
+
 int vsel::lis_scores_stage(hipStream_t st, const void* h, vsel_dtype hdtype, const vsel_segments* seg, const vsel_scorer* sc, char* ws,
                            const LisPlan& p, float* scores, const int64_t* out_map, const float* col_sums, bool small) {
-  return with_dtypes(hdtype, sc->wdtype, [&](auto t, auto tw) {
+  return with_dtype(hdtype, [&](auto t) {
     using T = decltype(t);
     const T* hp = (const T*)h;
     int rc;
@@ -41,7 +67,7 @@ int vsel::lis_scores_stage(hipStream_t st, const void* h, vsel_dtype hdtype, con
       if ((rc = run_proj_small(st, seg, sc, ws, p, col_sums))) return rc;
       return run_score_small<T>(st, hp, seg, sc, ws, p, scores, out_map);
     }
-    if ((rc = run_proj<decltype(tw)>(st, seg, sc, ws, p, col_sums))) return rc;
+    if ((rc = run_proj(st, seg, sc, ws, p, col_sums))) return rc;
     return run_score<T>(st, hp, seg, sc, ws, p, scores, out_map);
   });
 }
@@ -111,15 +137,12 @@ extern "C" int vsel_gather_rows(void* stream, const void* h, vsel_dtype hdtype, 
   if (((uintptr_t)h | (uintptr_t)out) & 15) return fail(VSEL_ERR_INVALID, "h / out must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   VSEL_PROF_BEGIN(s);
-  if (hdtype == VSEL_BF16) {
-    if (d % 8) return fail(VSEL_ERR_UNSUPPORTED, "D must be a multiple of 8");
-    return launch_gather<bf16_t>(s, (const bf16_t*)h, (int)d, seg, idx, (bf16_t*)out);
-  }
-  if (hdtype == VSEL_F32) {
-    if (d % 4) return fail(VSEL_ERR_UNSUPPORTED, "D must be a multiple of 4");
-    return launch_gather<float>(s, (const float*)h, (int)d, seg, idx, (float*)out);
-  }
-  return fail(VSEL_ERR_INVALID, "bad dtype");
+  if (hdtype != VSEL_BF16 && hdtype != VSEL_F32) return fail(VSEL_ERR_INVALID, "bad dtype");
+  return with_dtype(hdtype, [&](auto t) {
+    using T = decltype(t);
+    if (d % Elem<T>::kVec) return fail(VSEL_ERR_UNSUPPORTED, "D must be a multiple of %d", Elem<T>::kVec);
+    return launch_gather<T>(s, (const T*)h, (int)d, seg, idx, (T*)out);
+  });
 }
 
 extern "C" int vsel_lis_select(void* stream, const void* h, vsel_dtype hdtype, const vsel_segments* seg,

@@ -10,24 +10,17 @@
 // projections [S, D] x [D, Hd] and [S, Hd] x [Hd, D] which run on the fp32-input MFMA
 // (v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation, so index selection can be compared
 // bit-for-bit with the fp32 CPU oracle on tie-free inputs).
+// Kernels and launchers, compiled once (lis.hip is the only includer); plan, checks and the launchers' prototypes: lis_stages.h.
 #pragma once
-#include "common.h"
-#ifndef VSEL_PROJ_WAVES
-#define VSEL_PROJ_WAVES 4
+#ifndef VSEL_LIS_KERNELS_TU
+#error "lis_kernels.h holds __global__ kernels and is compiled once, in lis.hip: include lis_stages.h and call its launchers instead"
 #endif
+#include "lis_stages.h"
 #include "proj_bf16x3.h"
-#include <algorithm>
-#include <type_traits>
-#include <math.h>
 
 namespace vsel {
 
 // =================================================================================================
-constexpr int kProjWaves = VSEL_PROJ_WAVES;   // waves per workgroup of the bf16x3 projection GEMMs (independent waves sharing one operand tile through L1)
-constexpr int kRowsPerChunk = 128;   // sweep-1 row chunk (batch-invariant summation order)
-constexpr int kSliceNT = 256;        // split-K slice of the kbar projection (fixed => batch-invariant)
-constexpr int kSliceNN = 128;        // split-K slice of the w projection
-
 // K1  partial column sums.  grid (col_tiles, row_splits, n_seg), block 256 (4 waves).
 //     A wave reads 64 lanes x 16 B = 1 KiB contiguous of one row; the block's 4 waves interleave rows and reduce through
 //     LDS.  (A barrier-free variant -- each wave owning a whole column tile of the chunk -- is 2 % faster in isolation
@@ -37,19 +30,6 @@ constexpr int kSliceNN = 128;        // split-K slice of the w projection
 // NT: non-temporal loads (the token tensor is streamed once per sweep and does not fit the caches); chosen per launch by
 // stream_policy() -- below ~384 MB the default policy is faster because sweep 2 and the gather hit what sweep 1 left in the
 // Infinity Cache (tools/exp_small_batch.py: B = 8 images 86 vs 96 us, B = 32 271 vs 238 us).  Results are identical.
-template <typename T> __device__ __forceinline__ void unpack_vec(u32x4 raw, float (&v)[Elem<T>::kVec]);
-template <> __device__ __forceinline__ void unpack_vec<bf16_t>(u32x4 raw, float (&v)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(raw[i] << 16);
-    v[2 * i + 1] = __uint_as_float(raw[i] & 0xffff0000u);
-  }
-}
-template <> __device__ __forceinline__ void unpack_vec<float>(u32x4 raw, float (&v)[4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[i] = __uint_as_float(raw[i]);
-}
-
 template <typename T, bool NT, bool DEEP = false>
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict__ h, SegView sv, int d,
                                                              int row_splits, float* __restrict__ partial) {
@@ -275,7 +255,7 @@ __global__ __launch_bounds__(256) void colsum_seg_kernel(const T* __restrict__ h
 }
 
 // K1b  xbar[s][c] = sum_rs partial[s][rs][c] / N_s   (fixed order)
-static __attribute__((unused)) __global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restrict__ partial, SegView sv, int d,
+__global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restrict__ partial, SegView sv, int d,
                                                             int row_splits, float* __restrict__ xbar) {
   const int s = blockIdx.y;
   const int c = blockIdx.x * 256 + threadIdx.x;
@@ -347,6 +327,14 @@ __global__ __launch_bounds__(64) void gemm_nt_kernel(const float* __restrict__ x
   }
 }
 
+int launch_gemm_nt(hipStream_t st, vsel_dtype wdtype, const float* x, const void* w, int M, int N, int K, int kslice, int ks, float* part) {
+  const dim3 grid((unsigned)cdiv(N, 32), (unsigned)cdiv(M, 32), ks);
+  if (wdtype == VSEL_BF16) VSEL_LAUNCH(gemm_nt_kernel<bf16_t>, grid, dim3(64), 0, st, x, (const bf16_t*)w, M, N, K, kslice, part);
+  else VSEL_LAUNCH(gemm_nt_kernel<float>, grid, dim3(64), 0, st, x, (const float*)w, M, N, K, kslice, part);
+  VSEL_AFTER_LAUNCH(st, "gemm_nt_kernel");
+  return VSEL_OK;
+}
+
 // K2b  kbar[m][n] = sum_ks part[ks][m][n] + bk[n];  c[m] = sum_n bq[n] * kbar[m][n].  One block per m.
 template <typename TW>
 __global__ __launch_bounds__(256) void kbar_finish_kernel(const float* __restrict__ part, int KS, int M, int N,
@@ -373,6 +361,13 @@ __global__ __launch_bounds__(256) void kbar_finish_kernel(const float* __restric
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cacc;
   __syncthreads();
   if (threadIdx.x == 0) c[m] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+int launch_kbar_finish(hipStream_t st, vsel_dtype wdtype, const float* part, int ks, int M, int N, const void* bk, const void* bq, float* kbar, float* c) {
+  if (wdtype == VSEL_BF16) VSEL_LAUNCH(kbar_finish_kernel<bf16_t>, dim3(M), dim3(256), 0, st, part, ks, M, N, (const bf16_t*)bk, (const bf16_t*)bq, kbar, c);
+  else VSEL_LAUNCH(kbar_finish_kernel<float>, dim3(M), dim3(256), 0, st, part, ks, M, N, (const float*)bk, (const float*)bq, kbar, c);
+  VSEL_AFTER_LAUNCH(st, "kbar_finish_kernel");
+  return VSEL_OK;
 }
 
 // =================================================================================================
@@ -443,13 +438,24 @@ __global__ __launch_bounds__(64) void gemm_nn_kernel(const float* __restrict__ x
 }
 
 // K3b  out[e] = sum_ks part[ks][e]
-static __attribute__((unused)) __global__ __launch_bounds__(256) void slice_sum_kernel(const float* __restrict__ part, int KS, int64_t count,
+__global__ __launch_bounds__(256) void slice_sum_kernel(const float* __restrict__ part, int KS, int64_t count,
                                                         float* __restrict__ out) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= count) return;
   float v = 0.f;
   for (int ks = 0; ks < KS; ++ks) v += part[(int64_t)ks * count + e];
   out[e] = v;
+}
+
+// K3 + K3b: out[m][n] = sum_k x[m][k] w[k][n] through the split-K slabs `part`
+int launch_gemm_nn(hipStream_t st, vsel_dtype wdtype, const float* x, const void* w, int M, int N, int K, int kslice, int ks, float* part, float* out) {
+  const dim3 grid((unsigned)cdiv(N, 256), (unsigned)cdiv(M, 32), ks);
+  if (wdtype == VSEL_BF16) VSEL_LAUNCH(gemm_nn_kernel<bf16_t>, grid, dim3(64), 0, st, x, (const bf16_t*)w, M, N, K, kslice, part);
+  else VSEL_LAUNCH(gemm_nn_kernel<float>, grid, dim3(64), 0, st, x, (const float*)w, M, N, K, kslice, part);
+  VSEL_AFTER_LAUNCH(st, "gemm_nn_kernel");
+  VSEL_LAUNCH(slice_sum_kernel, dim3((unsigned)cdiv((int64_t)M * N, 256)), dim3(256), 0, st, part, ks, (int64_t)M * N, out);
+  VSEL_AFTER_LAUNCH(st, "slice_sum_kernel");
+  return VSEL_OK;
 }
 
 template <typename T>
@@ -588,14 +594,7 @@ __global__ __launch_bounds__(256) void score_kernel(const T* __restrict__ h, Seg
 //     compaction pass (ballot + popcount prefix) that emits ascending indices -- the reference's
 //     topk(k).indices.sort() without a sort.  One block of 1024 threads per segment.
 // =================================================================================================
-__device__ __forceinline__ uint32_t order_key(float x) {
-  const float f = x + 0.0f;  // -0.0 -> +0.0
-  const uint32_t u = __float_as_uint(f);
-  if (f != f) return 0xffffffffu;  // NaN sorts greatest (torch.topk convention)
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-static __attribute__((unused)) __global__ __launch_bounds__(1024) void topk_select_kernel(const float* __restrict__ scores, SegView sv,
+__global__ __launch_bounds__(1024) void topk_select_kernel(const float* __restrict__ scores, SegView sv,
                                                            int64_t* __restrict__ idx, float* __restrict__ mask) {
   const int s = blockIdx.x;
   const int n = sv.n_rows(s);
@@ -854,116 +853,19 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const T* __restrict__ 
 // =================================================================================================
 // host side
 // =================================================================================================
-// Cache policy of the three kernels that touch the token tensor: non-temporal once the tensor clearly exceeds the Infinity
-// Cache (256 MB) + L2 (32 MB).  Measured crossover between 264 MB (default policy 4 % faster) and 528 MB (nt 12 % faster).
-constexpr int64_t kStreamBytes = 384ll << 20;
-inline bool stream_policy(int64_t total_rows, int64_t d, size_t elem) { return total_rows * d * (int64_t)elem >= kStreamBytes; }
-
-struct LisPlan {
-  int64_t S, maxn, d, hd;
-  int row_splits;
-  int ks1, kslice1;  // kbar projection  [S, D] x [Hd, D]^T
-  int ks2, kslice2;  // w projection     [S, Hd] x [Hd, D]
-  int n_cpart;       // blocks of 256 over Hd
-  bool mfma_bf16;    // shapes allow the bf16x3 MFMA projections (K % 16 == 0); weights must also be bf16
-  size_t off_partial, off_xbar, off_part1, off_kbar, off_c, off_part2, off_w, off_xs, off_ksp, off_cpart, total;
-};
-
-inline LisPlan make_plan(int64_t S, int64_t maxn, int64_t d, int64_t hd) {
-  LisPlan p{};
-  p.S = S; p.maxn = maxn; p.d = d; p.hd = hd;
-  // Batch-invariant plan: the summation tree of one segment never depends on how many segments share the call
-  // (fixed 128-row chunks in sweep 1, fixed split-K slices in the projections), so batching and the ragged form
-  // reproduce a single-image call bit for bit.
-  p.row_splits = (int)std::max<int64_t>(1, cdiv(maxn, kRowsPerChunk));
-  p.mfma_bf16 = (d % 16 == 0) && (hd % 16 == 0);
-  p.kslice1 = (int)std::min<int64_t>(kSliceNT, cdiv(d, 16) * 16);
-  p.ks1 = (int)cdiv(d, p.kslice1);
-  p.kslice2 = (int)std::min<int64_t>(kSliceNN, cdiv(hd, 16) * 16);
-  p.ks2 = (int)cdiv(hd, p.kslice2);
-  p.n_cpart = (int)cdiv(hd, 8);
-  const int64_t m_pad = 32 * cdiv(S, 32);
-  size_t o = 0;
-  auto take = [&](size_t nfloat) { size_t r = o; o += align_up(nfloat * sizeof(float), 256); return r; };
-  p.off_partial = take((size_t)S * p.row_splits * d);
-  p.off_xbar = take((size_t)S * d);
-  p.off_part1 = take((size_t)p.ks1 * m_pad * hd);
-  p.off_kbar = take((size_t)S * hd);
-  p.off_c = take((size_t)S);
-  p.off_part2 = take((size_t)p.ks2 * m_pad * d);
-  p.off_w = take((size_t)S * d);
-  p.off_xs = take(((size_t)3 * m_pad * d + 1) / 2);
-  p.off_ksp = take(((size_t)3 * m_pad * hd + 1) / 2);
-  p.off_cpart = take((size_t)S * p.n_cpart);
-  p.total = o;
-  return p;
-}
-
-inline int check_segments_impl(const vsel_segments* seg, bool need_k) {
-  if (!seg) return fail(VSEL_ERR_INVALID, "segments is NULL");
-  if (seg->n_seg < 1 || seg->rows_per_seg < 1 || seg->total_rows < 1)
-    return fail(VSEL_ERR_INVALID, "empty segments (n_seg=%lld rows_per_seg=%lld total_rows=%lld)",
-                (long long)seg->n_seg, (long long)seg->rows_per_seg, (long long)seg->total_rows);
-  if (seg->n_seg > 65535) return fail(VSEL_ERR_UNSUPPORTED, "n_seg %lld > 65535", (long long)seg->n_seg);
-  if (seg->total_rows >= (1ll << 31)) return fail(VSEL_ERR_UNSUPPORTED, "total_rows must fit int32");
-  if (!seg->seg_rows && seg->total_rows != seg->n_seg * seg->rows_per_seg)
-    return fail(VSEL_ERR_INVALID, "uniform segments: total_rows != n_seg * rows_per_seg");
-  if (need_k) {
-    if (seg->k < 1 || seg->k > seg->rows_per_seg)
-      return fail(VSEL_ERR_INVALID, "k=%lld must satisfy 1 <= k <= rows_per_seg=%lld", (long long)seg->k,
-                  (long long)seg->rows_per_seg);
-    if ((seg->seg_rows != nullptr) != (seg->seg_out != nullptr))
-      return fail(VSEL_ERR_INVALID, "seg_rows and seg_out must both be given (ragged) or both NULL (uniform)");
-    if (!seg->seg_out && seg->total_out != seg->n_seg * seg->k)
-      return fail(VSEL_ERR_INVALID, "uniform segments: total_out != n_seg * k");
-  }
-  return VSEL_OK;
-}
-
-inline int check_scorer(const vsel_scorer* sc, vsel_dtype hdtype) {
-  if (!sc || !sc->wq || !sc->bq || !sc->wk || !sc->bk) return fail(VSEL_ERR_INVALID, "scorer parameter pointer is NULL");
-  if (sc->d < 8 || sc->hd < 1) return fail(VSEL_ERR_INVALID, "bad scorer dims d=%lld hd=%lld", (long long)sc->d, (long long)sc->hd);
-  if (sc->d % 8 != 0) return fail(VSEL_ERR_UNSUPPORTED, "in_features D=%lld must be a multiple of 8 (16-byte rows)", (long long)sc->d);
-  if (sc->wdtype != VSEL_BF16 && sc->wdtype != VSEL_F32) return fail(VSEL_ERR_INVALID, "bad weight dtype");
-  if (hdtype != VSEL_BF16 && hdtype != VSEL_F32) return fail(VSEL_ERR_INVALID, "bad token dtype");
-  return VSEL_OK;
-}
-
-// Calls f(T{}) / f(T{}, TW{}) with T the element type of the tokens (hdtype) and TW that of the scorer weights (wdtype): bf16_t or
-// float.  The dtypes have passed check_scorer (or the entry's own "bad dtype" check).
-template <typename F>
-inline int with_dtype(vsel_dtype hdtype, F&& f) {
-  return hdtype == VSEL_BF16 ? f(bf16_t{}) : f(float{});
-}
-template <typename F>
-inline int with_dtypes(vsel_dtype hdtype, vsel_dtype wdtype, F&& f) {
-  return with_dtype(hdtype, [&](auto t) { return wdtype == VSEL_BF16 ? f(t, bf16_t{}) : f(t, float{}); });
-}
-
-// Checks every entry with a scorer and a workspace shares: the scorer, then the workspace size (`need` = the entry's plan, made
-// once the scorer's dims are known good) and the 16-byte alignment of h, workspace and weights (`also`: one more pointer of the
-// entry's that `what` names).
-template <typename Need>
-inline int check_scorer_workspace(const void* h, vsel_dtype hdtype, const vsel_scorer* sc, const void* ws, size_t ws_bytes,
-                                  Need&& need, const char* what = "h / workspace / weights", const void* also = nullptr) {
-  int st = check_scorer(sc, hdtype);
-  if (st) return st;
-  const size_t total = need();
-  if (!ws || ws_bytes < total) return fail(VSEL_ERR_WORKSPACE, "workspace %zu B < required %zu B", ws_bytes, total);
-  if (((uintptr_t)h | (uintptr_t)ws | (uintptr_t)sc->wq | (uintptr_t)sc->wk | (uintptr_t)also) & 15)
-    return fail(VSEL_ERR_INVALID, "%s must be 16-byte aligned", what);
-  return VSEL_OK;
-}
-
+// stage 3: sweep 2 (scores) with the w, c that run_proj left in the workspace
 template <typename T>
-inline int launch_score(hipStream_t st, const T* h, const SegView& sv, const vsel_segments* seg, int d,
-                        const float* w, const float* c, int hd, float* scores, const int64_t* out_map = nullptr) {
+inline int run_score(hipStream_t st, const T* h, const vsel_segments* seg, const vsel_scorer* sc, char* ws, const LisPlan& p,
+                     float* scores, const int64_t* out_map = nullptr) {
   constexpr int V = Elem<T>::kVec;
+  const SegView sv = make_view(seg);
+  const int d = (int)sc->d;
+  const float *w = (const float*)(ws + p.off_w), *c = (const float*)(ws + p.off_c);
   // rows per block: keep >= ~2048 blocks when there is enough work, 8..64 rows per block
   int64_t rpb = 64;
   while (rpb > 8 && seg->n_seg * cdiv(seg->rows_per_seg, rpb) < 2048) rpb >>= 1;
   dim3 grid((unsigned)cdiv(seg->rows_per_seg, rpb), (unsigned)seg->n_seg);
-  const float sq = (float)sqrt((double)hd);
+  const float sq = (float)sqrt((double)sc->hd);
   const bool nt = stream_policy(seg->total_rows, d, sizeof(T));
   const int iters = (d % (64 * V) == 0) ? d / (64 * V) : 0;
 #define VSEL_SCORE_CASE(I)                                                                              \
@@ -981,26 +883,15 @@ inline int launch_score(hipStream_t st, const T* h, const SegView& sv, const vse
   return VSEL_OK;
 }
 
-// sweep 1 as colsum_seg_kernel (the segments' sums, one "chunk") instead of per-chunk partials: when some slab width (512 / 256 /
-// 128 bf16 columns) gives knob LIS_SEG_SUMS (segment, slab) pairs = waves (default 896 = 3.5 per CU; 0 = never; measured per call at
-// the 7B geometry, chunked vs this: B = 32 231 vs 228 us, 64 446 vs 428, 96 721 vs 685, 128 848-895 vs 826-830; with 672 pairs no
-// gain, with one 512-column slab per wave at B = 64 a loss: 483 vs 442), never for the <= 8 segments the small-batch form may take
-// (its kernels rebuild x-bar from chunk partials), more than one chunk, and no segment longer than 1.375 x the average: a wave
-// streams its (segment, slab) alone, at most twice as fast once the others are done, so the longest segment's waves finish last --
-// tools/exp_ragged_lis.py, profiles/r04_ragged_lis.txt, call time chunked vs this form by max / mean: 1.0 +1.5 %, 1.13 +1.8 ... +3.2 %,
-// 1.33 +1.2 ... 0 %, 1.5 - 1.7 (N_i ~ U{576..4096}) -4 % (32 prompts), -7 % (64), -10 % (128: sweep 1 446 -> 336 us).  Same sums bit for
-// bit either way: batch invariance is untouched.
-inline bool seg_sums_form(const LisPlan& p, const vsel_segments* seg) {
-  const int mn = knob(VSEL_KNOB_LIS_SEG_SUMS);
-  // (pairs counted for the narrowest slab of bf16 tokens, 128 columns, whatever the token type: the projection stage does not know it)
-  return mn > 0 && p.S > 8 && p.S * cdiv(p.d, 128) >= mn && p.row_splits > 1 && p.d % 8 == 0 && seg->total_rows * 11 >= (int64_t)p.S * p.maxn * 8;
-}
-
+// stage 1: sweep 1 (column-sum partials, or the segments' sums and bf16x3 planes of the mean: seg_sums_form)
 template <typename T>
-inline int launch_colsum(hipStream_t st, const T* h, const SegView& sv, int d, int S, int row_splits, float* partial,
-                         int64_t total_rows, bool seg_sums = false, uint16_t* xs = nullptr) {
+inline int run_colsum(hipStream_t st, const T* h, const vsel_segments* seg, int d, char* ws, const LisPlan& p) {
   constexpr int V = Elem<T>::kVec;
-  if (seg_sums) {
+  const SegView sv = make_view(seg);
+  const int S = (int)seg->n_seg, row_splits = p.row_splits;
+  float* partial = (float*)(ws + p.off_partial);
+  if (seg_sums_form(p, seg)) {
+    uint16_t* xs = p.mfma_bf16 ? (uint16_t*)(ws + p.off_xs) : nullptr;
     // the widest slab (16- / 8- / 4-byte loads per lane) that still gives knob LIS_SEG_SUMS (segment, slab) pairs
     const int mn = std::max(1, knob(VSEL_KNOB_LIS_SEG_SUMS));
     const int epw = sizeof(T) == 2 ? 2 : 1;                       // elements per 32-bit word
@@ -1008,7 +899,7 @@ inline int launch_colsum(hipStream_t st, const T* h, const SegView& sv, int d, i
     while (nw > 1 && ((int64_t)S * cdiv(d, 64 * nw * epw) < mn || d % (nw * epw) != 0)) nw >>= 1;
     const int col_tiles = (int)cdiv(d, 64 * nw * epw);
     const dim3 g2((unsigned)cdiv((int64_t)col_tiles * S, 4));
-    const bool nt = stream_policy(total_rows, d, sizeof(T));
+    const bool nt = stream_policy(seg->total_rows, d, sizeof(T));
 #define VSEL_SEG_LAUNCH(NWV)                                                                                                    \
     do {                                                                                                                        \
       if (nt) VSEL_LAUNCH((colsum_seg_kernel<T, true, NWV>), g2, dim3(256), 0, st, h, sv, d, col_tiles, S, partial, xs); \
@@ -1022,7 +913,7 @@ inline int launch_colsum(hipStream_t st, const T* h, const SegView& sv, int d, i
   const dim3 grid((unsigned)cdiv(d, 64 * V), row_splits, S);
   if ((int64_t)grid.x * grid.y * grid.z <= 1024)       // <= one workgroup per SIMD-quad: latency-bound, use the deep form
     VSEL_LAUNCH((colsum_partial_kernel<T, false, true>), grid, dim3(256), 0, st, h, sv, d, row_splits, partial);
-  else if (stream_policy(total_rows, d, sizeof(T)))
+  else if (stream_policy(seg->total_rows, d, sizeof(T)))
     VSEL_LAUNCH((colsum_partial_kernel<T, true>), grid, dim3(256), 0, st, h, sv, d, row_splits, partial);
   else
     VSEL_LAUNCH((colsum_partial_kernel<T, false>), grid, dim3(256), 0, st, h, sv, d, row_splits, partial);
@@ -1030,32 +921,16 @@ inline int launch_colsum(hipStream_t st, const T* h, const SegView& sv, int d, i
   return VSEL_OK;
 }
 
-// stage 1: sweep 1 (column-sum partials)
-template <typename T>
-inline int run_colsum(hipStream_t st, const T* h, const vsel_segments* seg, int d, char* ws, const LisPlan& p) {
-  return launch_colsum<T>(st, h, make_view(seg), d, (int)seg->n_seg, p.row_splits, (float*)(ws + p.off_partial), seg->total_rows,
-                          seg_sums_form(p, seg), p.mfma_bf16 ? (uint16_t*)(ws + p.off_xs) : nullptr);
-}
-
-// The bf16x3 projections with their split-K slices summed in LDS (gemm_nt_sum / gemm_nn_sum_bf16x3_kernel: two launches, no slabs)
-// instead of slab GEMM + finish kernel twice (four launches): knob LIS_PROJ_SUM 0 never, 1 whenever both projections have at most
-// kSumMaxSlices K-slices (one wave per slice in one workgroup), -1 (default) from kProjSumMinSeg segments.  Same bits either way.
-// Measured (tools/ab_proj.py, profiles/proj_sum_ab.txt; us of the four / two projection launches, forms alternated, 7B geometry): 8 images
-// 34.7 / 30.6 with the step 83-90 / 85, 16 images 37.0 / 41.2, 32 images 38.6 / 41.2 (one m-tile: one workgroup per 32 weight rows leaves
-// most CUs idle, the slab form's 14 slices on 14 CUs win), 64 images 43.6 / 35.7 (step 431-448 / 428-429), 128 images 55.1 / 36.9
-// (step 855-857 / 812-844), 3B x 512 60.1 / 43.0, LLaVA-OV x 48 (16 slices) 47.4 / 36.7: a gain from two m-tiles on, and 48 segments is
-// the smallest count at which one was measured.
-constexpr int kProjSumMinSeg = 48;
-inline bool proj_sum_form(const LisPlan& p) {
-  const int f = knob(VSEL_KNOB_LIS_PROJ_SUM);
-  if (f == 0 || p.ks1 > kSumMaxSlices || p.ks2 > kSumMaxSlices || p.d * p.hd >= (1ll << 30)) return false;      // (32-bit weight offsets)
-  return f > 0 || (p.S > 8 && p.S >= kProjSumMinSeg);
+// (kernel in proj_bf16x3.h; launched from here so that every launch name of the inference step is in this file or lis_small.h)
+int launch_colsum_finish_split(hipStream_t st, const float* partial, const SegView& sv, int d, int row_splits, int M, uint16_t* xs) {
+  VSEL_LAUNCH(colsum_finish_split_kernel, dim3((unsigned)cdiv(d, 256), M), dim3(256), 0, st, partial, sv, d, row_splits, M, xs);
+  VSEL_AFTER_LAUNCH(st, "colsum_finish_split_kernel");
+  return VSEL_OK;
 }
 
 // stage 2: partials -> xbar -> kbar -> (w, c)   (small, latency-bound kernels)
 // col_sums (optional): [S, D] fp32 column sums of the tokens supplied by the producer (vsel_lis_select_presummed); they take
 // the place of the sweep-1 partials as a single "chunk", everything downstream is unchanged.
-template <typename TW>
 inline int run_proj(hipStream_t st, const vsel_segments* seg, const vsel_scorer* sc, char* ws, const LisPlan& p_in,
                     const float* col_sums = nullptr) {
   const SegView sv = make_view(seg);
@@ -1069,80 +944,49 @@ inline int run_proj(hipStream_t st, const vsel_segments* seg, const vsel_scorer*
   float* c = (float*)(ws + p.off_c);
   float* part2 = (float*)(ws + p.off_part2);
   float* w = (float*)(ws + p.off_w);
-  if constexpr (std::is_same<TW, bf16_t>::value) {
-    if (p.mfma_bf16) {
-      // bf16x3 MFMA projections (proj_bf16x3.h)
-      uint16_t* xs = (uint16_t*)(ws + p.off_xs);
-      uint16_t* ksp = (uint16_t*)(ws + p.off_ksp);
-      float* cpart = (float*)(ws + p.off_cpart);
-      if (col_sums || !seg_sums_form(p_in, seg)) {       // (colsum_seg_kernel leaves the planes itself)
-        VSEL_LAUNCH(colsum_finish_split_kernel, dim3((unsigned)cdiv(d, 256), S), dim3(256), 0, st, partial, sv, d,
-                           p.row_splits, S, xs);
-        VSEL_AFTER_LAUNCH(st, "colsum_finish_split_kernel");
-      }
-      const unsigned mtiles = (unsigned)cdiv(S, 32);
-      const int m_pad = 32 * (int)mtiles;
-      if (proj_sum_form(p)) {
-        // split-K summed in LDS (proj_bf16x3.h): the two finish launches and both slabs are gone, same bits
-        VSEL_LAUNCH(gemm_nt_sum_bf16x3_kernel, dim3((unsigned)cdiv(hd, 32), mtiles), dim3(64 * p.ks1), 0, st, xs, (const uint16_t*)sc->wk,
-                           S, hd, d, p.kslice1, p.ks1, (int)mtiles, (const uint16_t*)sc->bk, (const uint16_t*)sc->bq, kbar, ksp, cpart,
-                           p.n_cpart);
-        VSEL_AFTER_LAUNCH(st, "gemm_nt_bf16x3_kernel");
-        VSEL_LAUNCH(gemm_nn_sum_bf16x3_kernel, dim3((unsigned)cdiv(d, 64), mtiles), dim3(64 * p.ks2), 0, st, ksp, (const uint16_t*)sc->wq,
-                           S, d, hd, p.kslice2, p.ks2, (int)mtiles, cpart, p.n_cpart, w, c);
-        VSEL_AFTER_LAUNCH(st, "gemm_nn_bf16x3_kernel");
-        return VSEL_OK;
-      }
-      VSEL_LAUNCH(gemm_nt_bf16x3_kernel<kProjWaves>, dim3((unsigned)cdiv(hd, 64), (unsigned)cdiv(mtiles, kProjWaves), p.ks1), dim3(64 * kProjWaves), 0, st, xs,
-                         (const uint16_t*)sc->wk, S, hd, d, p.kslice1, part1, (int)mtiles);
+  int rc;
+  if (sc->wdtype == VSEL_BF16 && p.mfma_bf16) {
+    // bf16x3 MFMA projections (proj_bf16x3.h)
+    uint16_t* xs = (uint16_t*)(ws + p.off_xs);
+    uint16_t* ksp = (uint16_t*)(ws + p.off_ksp);
+    float* cpart = (float*)(ws + p.off_cpart);
+    // (colsum_seg_kernel leaves the planes itself)
+    if ((col_sums || !seg_sums_form(p_in, seg)) && (rc = launch_colsum_finish_split(st, partial, sv, d, p.row_splits, S, xs))) return rc;
+    const unsigned mtiles = (unsigned)cdiv(S, 32);
+    const int m_pad = 32 * (int)mtiles;
+    if (proj_sum_form(p)) {
+      // split-K summed in LDS (proj_bf16x3.h): the two finish launches and both slabs are gone, same bits
+      VSEL_LAUNCH(gemm_nt_sum_bf16x3_kernel, dim3((unsigned)cdiv(hd, 32), mtiles), dim3(64 * p.ks1), 0, st, xs, (const uint16_t*)sc->wk,
+                         S, hd, d, p.kslice1, p.ks1, (int)mtiles, (const uint16_t*)sc->bk, (const uint16_t*)sc->bq, kbar, ksp, cpart,
+                         p.n_cpart);
       VSEL_AFTER_LAUNCH(st, "gemm_nt_bf16x3_kernel");
-      VSEL_LAUNCH(kbar_finish_split_kernel, dim3(mtiles, p.n_cpart), dim3(256), 0, st, part1, p.ks1, S, hd, m_pad,
-                         (const uint16_t*)sc->bk, (const uint16_t*)sc->bq, kbar, ksp, cpart);
-      VSEL_AFTER_LAUNCH(st, "kbar_finish_split_kernel");
-      VSEL_LAUNCH(gemm_nn_bf16x3_kernel<kProjWaves>, dim3((unsigned)cdiv(d, 256), (unsigned)cdiv(mtiles, kProjWaves), p.ks2), dim3(64 * kProjWaves), 0, st, ksp,
-                         (const uint16_t*)sc->wq, S, d, hd, p.kslice2, part2, (int)mtiles);
+      VSEL_LAUNCH(gemm_nn_sum_bf16x3_kernel, dim3((unsigned)cdiv(d, 64), mtiles), dim3(64 * p.ks2), 0, st, ksp, (const uint16_t*)sc->wq,
+                         S, d, hd, p.kslice2, p.ks2, (int)mtiles, cpart, p.n_cpart, w, c);
       VSEL_AFTER_LAUNCH(st, "gemm_nn_bf16x3_kernel");
-      VSEL_LAUNCH(w_finish_kernel, dim3(mtiles, (unsigned)cdiv(d, 8)), dim3(256), 0, st, part2, p.ks2, S, d, m_pad,
-                         cpart, p.n_cpart, w, c);
-      VSEL_AFTER_LAUNCH(st, "w_finish_kernel");
       return VSEL_OK;
     }
+    if ((rc = launch_gemm_nt_bf16x3(st, xs, (const uint16_t*)sc->wk, S, hd, d, p.kslice1, p.ks1, part1))) return rc;
+    VSEL_LAUNCH(kbar_finish_split_kernel, dim3(mtiles, p.n_cpart), dim3(256), 0, st, part1, p.ks1, S, hd, m_pad,
+                       (const uint16_t*)sc->bk, (const uint16_t*)sc->bq, kbar, ksp, cpart);
+    VSEL_AFTER_LAUNCH(st, "kbar_finish_split_kernel");
+    VSEL_LAUNCH(gemm_nn_bf16x3_kernel<kProjWaves>, dim3((unsigned)cdiv(d, 256), (unsigned)cdiv(mtiles, kProjWaves), p.ks2), dim3(64 * kProjWaves), 0, st, ksp,
+                       (const uint16_t*)sc->wq, S, d, hd, p.kslice2, part2, (int)mtiles);
+    VSEL_AFTER_LAUNCH(st, "gemm_nn_bf16x3_kernel");
+    VSEL_LAUNCH(w_finish_kernel, dim3(mtiles, (unsigned)cdiv(d, 8)), dim3(256), 0, st, part2, p.ks2, S, d, m_pad,
+                       cpart, p.n_cpart, w, c);
+    VSEL_AFTER_LAUNCH(st, "w_finish_kernel");
+    return VSEL_OK;
   }
   // generic path: fp32-input MFMA (fp32 weights, or K not a multiple of 16)
   VSEL_LAUNCH(colsum_finish_kernel, dim3((unsigned)cdiv(d, 256), S), dim3(256), 0, st, partial, sv, d,
                      p.row_splits, xbar);
   VSEL_AFTER_LAUNCH(st, "colsum_finish_kernel");
-  VSEL_LAUNCH((gemm_nt_kernel<TW>), dim3((unsigned)cdiv(hd, 32), (unsigned)cdiv(S, 32), p.ks1), dim3(64), 0, st,
-                     xbar, (const TW*)sc->wk, S, hd, d, p.kslice1, part1);
-  VSEL_AFTER_LAUNCH(st, "gemm_nt_kernel");
-  VSEL_LAUNCH((kbar_finish_kernel<TW>), dim3(S), dim3(256), 0, st, part1, p.ks1, S, hd, (const TW*)sc->bk,
-                     (const TW*)sc->bq, kbar, c);
-  VSEL_AFTER_LAUNCH(st, "kbar_finish_kernel");
-  VSEL_LAUNCH((gemm_nn_kernel<TW>), dim3((unsigned)cdiv(d, 256), (unsigned)cdiv(S, 32), p.ks2), dim3(64), 0, st,
-                     kbar, (const TW*)sc->wq, S, d, hd, p.kslice2, part2);
-  VSEL_AFTER_LAUNCH(st, "gemm_nn_kernel");
-  VSEL_LAUNCH(slice_sum_kernel, dim3((unsigned)cdiv((int64_t)S * d, 256)), dim3(256), 0, st, part2, p.ks2,
-                     (int64_t)S * d, w);
-  VSEL_AFTER_LAUNCH(st, "slice_sum_kernel");
-  return VSEL_OK;
+  if ((rc = launch_gemm_nt(st, sc->wdtype, xbar, sc->wk, S, hd, d, p.kslice1, p.ks1, part1))) return rc;
+  if ((rc = launch_kbar_finish(st, sc->wdtype, part1, p.ks1, S, hd, sc->bk, sc->bq, kbar, c))) return rc;
+  return launch_gemm_nn(st, sc->wdtype, kbar, sc->wq, S, d, hd, p.kslice2, p.ks2, part2, w);
 }
 
-// stage 3: sweep 2 (scores)
-template <typename T>
-inline int run_score(hipStream_t st, const T* h, const vsel_segments* seg, const vsel_scorer* sc, char* ws, const LisPlan& p,
-                     float* scores, const int64_t* out_map = nullptr) {
-  return launch_score<T>(st, h, make_view(seg), seg, (int)sc->d, (const float*)(ws + p.off_w), (const float*)(ws + p.off_c),
-                         (int)sc->hd, scores, out_map);
-}
-
-// The scores stage of every LIS entry (lis.hip, compiled there once): column sums unless the caller supplies col_sums, then the
-// small-batch form (lis_small.h) or the batched form of projections + score sweep -- the same bits either way.  The caller decides
-// `small`: the inference entries pass knob LIS_SMALL_PATH and small_path_ok(), training passes small_path_ok() alone (one segment
-// per call; the knob tunes inference batches and never reaches the training block).  hdtype / sc have passed check_scorer.
-int lis_scores_stage(hipStream_t st, const void* h, vsel_dtype hdtype, const vsel_segments* seg, const vsel_scorer* sc, char* ws,
-                     const LisPlan& p, float* scores, const int64_t* out_map, const float* col_sums, bool small);
-
-inline int launch_select(hipStream_t st, const float* scores, const vsel_segments* seg, int64_t* idx, float* mask) {
+int launch_select(hipStream_t st, const float* scores, const vsel_segments* seg, int64_t* idx, float* mask) {
   const int64_t maxn = seg->rows_per_seg;            // (= the longest segment for ragged calls)
   if (maxn <= 4 * 1024)
     VSEL_LAUNCH(topk_select_reg_kernel<4>, dim3((unsigned)seg->n_seg), dim3(1024), 0, st, scores, make_view(seg), idx, mask);
@@ -1267,9 +1111,7 @@ per_segment_form:
   switch (iters) {
     VSEL_GATHER_CASE(1) VSEL_GATHER_CASE(2) VSEL_GATHER_CASE(3) VSEL_GATHER_CASE(4)
     VSEL_GATHER_CASE(5) VSEL_GATHER_CASE(6) VSEL_GATHER_CASE(7) VSEL_GATHER_CASE(8)
-    default:
-      if (nt) VSEL_LAUNCH((gather_rows_kernel<T, true, 0>), grid, dim3(256), 0, st, h, make_view(seg), d, idx, out, (int)rpb, src_map);
-      else VSEL_LAUNCH((gather_rows_kernel<T, false, 0>), grid, dim3(256), 0, st, h, make_view(seg), d, idx, out, (int)rpb, src_map);
+    VSEL_GATHER_CASE(0)      // (iters is 0 for every other width)
   }
 #undef VSEL_GATHER_CASE
   VSEL_AFTER_LAUNCH(st, "gather_rows_kernel");

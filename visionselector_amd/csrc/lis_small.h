@@ -12,13 +12,15 @@
 // The arithmetic is the batched form's, operation for operation: same 128-row sweep-1 chunks, same bf16x3 planes, same MFMA
 // sequence per (tile, 256 / 128-wide k-slice), same slab order, same integer select -- scores, indices and rows are bit-identical
 // to the nine-launch path (tests/test_lis_gpu.py::test_small_batch_path_is_bit_identical).
+// Compiled once (lis.hip is the only includer); kSmallMaxSeg, small_path_ok / use_small_path and launch_proj_nt_small(_pair): lis_stages.h.
 #pragma once
+#ifndef VSEL_LIS_KERNELS_TU
+#error "lis_small.h holds __global__ kernels and is compiled once, in lis.hip: include lis_stages.h and call its launchers instead"
+#endif
 #include "lis_kernels.h"
-#include <stdlib.h>
 
 namespace vsel {
 
-constexpr int kSmallMaxSeg = 8;            // rows of the M dimension a workgroup rebuilds in its prologue
 constexpr int kSmallSelectThreads = 256;
 
 // -------------------------------------------------------------------------------------------------------------------------
@@ -129,7 +131,7 @@ __device__ __forceinline__ void proj_nt_small_body(const float* __restrict__ par
   VSEL_STAMP_DRAIN(1, 3);
 }
 
-static __attribute__((unused)) __global__ __launch_bounds__(64) void proj_nt_small_kernel(const float* __restrict__ partial, SegView sv, int S, int row_splits,
+__global__ __launch_bounds__(64) void proj_nt_small_kernel(const float* __restrict__ partial, SegView sv, int S, int row_splits,
                                                                   const uint16_t* __restrict__ w, int N, int K, int kslice,
                                                                   float* __restrict__ part, int64_t split_stride, int mean) {
   proj_nt_small_body(partial, sv, S, row_splits, w, N, K, kslice, part, split_stride, mean);
@@ -137,7 +139,7 @@ static __attribute__((unused)) __global__ __launch_bounds__(64) void proj_nt_sma
 
 // Two independent P1 products of the same shape in ONE launch (training backward: kbar = Wk xbar and dk_raw = Wq (sum_i g_i x_i), both
 // from the weighted column-sum partials): grid (ceil(N / 32), KS, 2), blockIdx.z picks the operand set.  Same body, same bits.
-static __attribute__((unused)) __global__ __launch_bounds__(64) void proj_nt_small_pair_kernel(const float* __restrict__ partial0, const float* __restrict__ partial1,
+__global__ __launch_bounds__(64) void proj_nt_small_pair_kernel(const float* __restrict__ partial0, const float* __restrict__ partial1,
                                                                        SegView sv, int S, int row_splits, const uint16_t* __restrict__ w0,
                                                                        const uint16_t* __restrict__ w1, int N, int K, int kslice,
                                                                        float* __restrict__ part0, float* __restrict__ part1_, int64_t split_stride,
@@ -146,13 +148,21 @@ static __attribute__((unused)) __global__ __launch_bounds__(64) void proj_nt_sma
   else proj_nt_small_body(partial1, sv, S, row_splits, w1, N, K, kslice, part1_, split_stride, mean1);
 }
 
+int launch_proj_nt_small(hipStream_t st, const float* partial, const SegView& sv, int S, int row_splits, const uint16_t* w, int N, int K,
+                         int kslice, int ks, float* part, int64_t split_stride, int mean) {
+  VSEL_LAUNCH(proj_nt_small_kernel, dim3((unsigned)cdiv(N, 32), ks), dim3(64), 0, st, partial, sv, S, row_splits, w, N, K, kslice, part,
+              split_stride, mean);
+  VSEL_AFTER_LAUNCH(st, "proj_nt_small_kernel");
+  return VSEL_OK;
+}
+
 // -------------------------------------------------------------------------------------------------------------------------
 // P2  part2[ks][m][n] = sum_{h in slice ks} kbar[m][h] Wq[h][n],  kbar[m][h] = sum_ks1 part1[ks1][m][h] + bk[h] (prologue);
 //     workgroups of n-tile 0 also leave cpart[m][h / 8] = sum_{8 h} bq[h] kbar[m][h].  grid (ceil(N / 128), KS2), one wave:
 //     lane (i, kg) loads 8 bytes = Wq[h][n0 + 4 i .. + 3] per k-row, MFMA tile t takes column 4 i + t (four tiles, 96 MFMAs per
 //     wave; the 256-column / eight-tile form of the batched kernel spends 3.9 us in its 192 MFMAs at one image).
 // -------------------------------------------------------------------------------------------------------------------------
-static __attribute__((unused)) __global__ __launch_bounds__(64) void proj_nn_small_kernel(const float* __restrict__ part1, int KS1, int S,
+__global__ __launch_bounds__(64) void proj_nn_small_kernel(const float* __restrict__ part1, int KS1, int S,
                                                                   const uint16_t* __restrict__ bk, const uint16_t* __restrict__ bq,
                                                                   const uint16_t* __restrict__ w, int N, int K, int kslice,
                                                                   float* __restrict__ part2, float* __restrict__ cpart, int n_cpart) {
@@ -586,20 +596,6 @@ __global__ __launch_bounds__(256) void select_gather_small_kernel(const T* __res
 // -------------------------------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------------------------------
-inline bool small_path_ok(const vsel_segments* seg, const vsel_scorer* sc, const LisPlan& p) {
-  return seg->n_seg <= kSmallMaxSeg && sc->wdtype == VSEL_BF16 && p.mfma_bf16 && p.kslice1 <= kSliceNT && p.kslice2 <= kSliceNN &&
-         sc->d % 8 == 0 && sc->hd % 8 == 0;
-}
-
-// What the inference entries pass to lis_scores_stage: the form is used up to knob VSEL_KNOB_LIS_SMALL_PATH segments per call.
-// Measured on MI355X (Qwen2.5-VL-7B geometry, us per call, small form vs batched form): 1 image 36.2 vs 51.7, 2 images 43.8 vs
-// 55.8, 3 images 52.2 vs 60.8, 4 images 60.4 vs 65.3, 8 images 102.3 vs 86.2 -- the redundant prologues grow with the segment
-// count, so the default limit is 4.  VSEL_SMALL_PATH=<n> / the knob set the limit (0 = never; at most kSmallMaxSeg).
-static_assert(kSmallMaxSeg == 8, "common.hip clamps VSEL_KNOB_LIS_SMALL_PATH to 8");
-inline bool use_small_path(const vsel_segments* seg, const vsel_scorer* sc, const LisPlan& p) {
-  return seg->n_seg <= knob(VSEL_KNOB_LIS_SMALL_PATH) && small_path_ok(seg, sc, p);
-}
-
 // sweep 1 partials (or the producer's column sums) -> part2 slabs + c partials: two launches
 inline int run_proj_small(hipStream_t st, const vsel_segments* seg, const vsel_scorer* sc, char* ws, const LisPlan& p,
                           const float* col_sums) {
@@ -609,9 +605,8 @@ inline int run_proj_small(hipStream_t st, const vsel_segments* seg, const vsel_s
   float* part1 = (float*)(ws + p.off_part1);
   float* part2 = (float*)(ws + p.off_part2);
   float* cpart = (float*)(ws + p.off_cpart);
-  VSEL_LAUNCH(proj_nt_small_kernel, dim3((unsigned)cdiv(hd, 32), p.ks1), dim3(64), 0, st, partial, make_view(seg), S,
-                     row_splits, (const uint16_t*)sc->wk, hd, d, p.kslice1, part1, (int64_t)d, 1);
-  VSEL_AFTER_LAUNCH(st, "proj_nt_small_kernel");
+  if (int rc = launch_proj_nt_small(st, partial, make_view(seg), S, row_splits, (const uint16_t*)sc->wk, hd, d, p.kslice1, p.ks1, part1, (int64_t)d, 1))
+    return rc;
   VSEL_LAUNCH(proj_nn_small_kernel, dim3((unsigned)cdiv(d, 128), p.ks2), dim3(64), 0, st, part1, p.ks1, S,
                      (const uint16_t*)sc->bk, (const uint16_t*)sc->bq, (const uint16_t*)sc->wq, d, hd, p.kslice2, part2, cpart,
                      p.n_cpart);

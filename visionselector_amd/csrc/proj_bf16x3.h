@@ -18,8 +18,12 @@
 //   * split-K slabs are stored [ks][n][m_pad] (m fastest): an MFMA C column (32 lanes = 32 consecutive m) is one
 //     128-byte line per store instead of 32 scattered dwords
 //   * the NT kernel covers two 32-row weight tiles per wave, halving the re-reads of the activation planes
+// Compiled once (lis_kernels.h, in lis.hip, is the only includer); lis_stages.h declares the launchers.
 #pragma once
-#include "common.h"
+#ifndef VSEL_LIS_KERNELS_TU
+#error "proj_bf16x3.h holds __global__ kernels and is compiled once, in lis.hip: include lis_stages.h and call its launchers instead"
+#endif
+#include "lis_stages.h"
 
 namespace vsel {
 
@@ -35,21 +39,6 @@ __device__ __forceinline__ void split3(float x, uint32_t& b1, uint32_t& b2, uint
   b3 = f32_to_bf16_bits(r2);
 }
 
-// sum_{j<n} p[j * stride] in index order.  24 loads in flight per batch, UNCONDITIONAL with a clamped index (a plain loop
-// serialises on latency; an 8-wide batch plus a scalar tail made 18 partials four round trips, 14 slabs seven)
-__device__ __forceinline__ float strided_sum(const float* __restrict__ p, int n, int64_t stride) {
-  float acc = 0.f;
-  for (int j = 0; j < n; j += 24) {
-    float v[24];
-#pragma unroll
-    for (int u = 0; u < 24; ++u) v[u] = p[(int64_t)min(j + u, n - 1) * stride];
-#pragma unroll
-    for (int u = 0; u < 24; ++u)
-      if (j + u < n) acc += v[u];
-  }
-  return acc;
-}
-
 // fragment-major offset (in bf16 elements) of activation element (m, k) of plane p; K % 16 == 0
 __device__ __forceinline__ int64_t frag_off(int p, int m, int k, int m_tiles, int k_steps) {
   const int mt = m >> 5, i = m & 31, ks = k >> 4, kg = (k >> 3) & 1, e = k & 7;
@@ -57,7 +46,7 @@ __device__ __forceinline__ int64_t frag_off(int p, int m, int k, int m_tiles, in
 }
 
 // xs (fragment-major bf16x3 planes) = split3( sum_rs partial[m][rs][c] / N_m )
-static __attribute__((unused)) __global__ __launch_bounds__(256) void colsum_finish_split_kernel(const float* __restrict__ partial, SegView sv,
+__global__ __launch_bounds__(256) void colsum_finish_split_kernel(const float* __restrict__ partial, SegView sv,
                                                                          int d, int row_splits, int M,
                                                                          uint16_t* __restrict__ xs) {
   const int s = blockIdx.y;
@@ -76,7 +65,7 @@ static __attribute__((unused)) __global__ __launch_bounds__(256) void colsum_fin
 // NT: part[ks][n][m_pad] = sum_{k in slice} x[m][k] w[n][k].  grid (ceil(N/64), m_tiles, KS), one wave per block:
 // two 32-row weight tiles x one 32-column activation tile.  Requires K % 16 == 0.  m_pad = 32 * m_tiles.
 template <int WPB>
-static __attribute__((unused)) __global__ __launch_bounds__(64 * WPB) void gemm_nt_bf16x3_kernel(const uint16_t* __restrict__ xs,
+__global__ __launch_bounds__(64 * WPB) void gemm_nt_bf16x3_kernel(const uint16_t* __restrict__ xs,
                                                                    const uint16_t* __restrict__ w, int /*M*/, int N, int K,
                                                                    int kslice, float* __restrict__ part, int m_tiles) {
   // WPB independent waves per workgroup on WPB m-tiles and the SAME weight tile: fetched from L2 once per CU.  Each wave's
@@ -148,9 +137,17 @@ static __attribute__((unused)) __global__ __launch_bounds__(64 * WPB) void gemm_
   }
 }
 
+int launch_gemm_nt_bf16x3(hipStream_t st, const uint16_t* xs, const uint16_t* w, int M, int N, int K, int kslice, int ks, float* part) {
+  const int mtiles = (int)cdiv(M, 32);
+  VSEL_LAUNCH(gemm_nt_bf16x3_kernel<kProjWaves>, dim3((unsigned)cdiv(N, 64), (unsigned)cdiv(mtiles, kProjWaves), ks), dim3(64 * kProjWaves), 0, st,
+              xs, w, M, N, K, kslice, part, mtiles);
+  VSEL_AFTER_LAUNCH(st, "gemm_nt_bf16x3_kernel");
+  return VSEL_OK;
+}
+
 // kbar[m][h] = sum_ks part[ks][h][m] + bk[h]  -> fp32 copy + fragment-major bf16x3 planes;
 // cpart[m][by] = sum_{h in block} bq[h] kbar[m][h].  grid (ceil(m_pad/32), ceil(N/8)), block 256 = 32 m x 8 h.
-static __attribute__((unused)) __global__ __launch_bounds__(256) void kbar_finish_split_kernel(const float* __restrict__ part, int KS, int M, int N,
+__global__ __launch_bounds__(256) void kbar_finish_split_kernel(const float* __restrict__ part, int KS, int M, int N,
                                                                        int m_pad, const uint16_t* __restrict__ bk,
                                                                        const uint16_t* __restrict__ bq,
                                                                        float* __restrict__ kbar, uint16_t* __restrict__ ksp,
@@ -187,7 +184,7 @@ static __attribute__((unused)) __global__ __launch_bounds__(256) void kbar_finis
 // register transpose (v_perm_b32) builds, for each t in 0..7, the A fragment {w[k0+8kg+e][n0+8i+t]}_e of the
 // 32x32 tile "n = n0 + 8*i' + t".  Requires K % 16 == 0 and N % 8 == 0.
 template <int WPB>
-static __attribute__((unused)) __global__ __launch_bounds__(64 * WPB) void gemm_nn_bf16x3_kernel(const uint16_t* __restrict__ xs,
+__global__ __launch_bounds__(64 * WPB) void gemm_nn_bf16x3_kernel(const uint16_t* __restrict__ xs,
                                                                    const uint16_t* __restrict__ w, int /*M*/, int N, int K,
                                                                    int kslice, float* __restrict__ part, int m_tiles) {
   // WPB independent waves per workgroup on WPB m-tiles and the SAME weight tile (72 % of this kernel's L2 traffic): fetched from
@@ -262,7 +259,7 @@ static __attribute__((unused)) __global__ __launch_bounds__(64 * WPB) void gemm_
 }
 
 // w[m][n] = sum_ks part[ks][n][m];  c[m] = sum_j cpart[m][j].  grid (ceil(m_pad/32), ceil(N/8)), block 256 = 32 m x 8 n.
-static __attribute__((unused)) __global__ __launch_bounds__(256) void w_finish_kernel(const float* __restrict__ part, int KS, int M, int N, int m_pad,
+__global__ __launch_bounds__(256) void w_finish_kernel(const float* __restrict__ part, int KS, int M, int N, int m_pad,
                                                               const float* __restrict__ cpart, int n_cpart,
                                                               float* __restrict__ w, float* __restrict__ c) {
   const int m = blockIdx.x * 32 + (threadIdx.x & 31);
@@ -290,8 +287,7 @@ static __attribute__((unused)) __global__ __launch_bounds__(256) void w_finish_k
 // launches, no hand-off between workgroups.  Every slice starts from a zero accumulator and runs the k-steps, operand layout
 // and MFMA order (b3, b2, b1) of the slab kernels above, so each output element is the slab path's bit for bit (an MFMA output
 // element depends on its own operand row and column only, not on where in the tile it sits).
-// Registers: up to 16 waves = 4 per SIMD, 128 registers each -- hence smaller tiles per wave than the slab kernels.
-constexpr int kSumMaxSlices = 16;      // waves per workgroup (1024 threads); a projection with more K-slices keeps the slab form
+// Registers: up to kSumMaxSlices = 16 waves = 4 per SIMD, 128 registers each -- hence smaller tiles per wave than the slab kernels.
 
 // sum_{s<n} p[s * stride] of LDS in index order, as strided_sum: every read in flight at once (clamped index), plain adds in order
 __device__ __forceinline__ float slice_sum(const float* p, int n, int stride) {
@@ -310,7 +306,7 @@ __device__ __forceinline__ float slice_sum(const float* p, int n, int stride) {
 // (One weight tile per wave, not the slab kernel's two: a lane's 16-byte weight load touches a cache line of its own, 64 lines per
 // instruction, and a workgroup issues those for all K; with 64-row tiles -- half the workgroups, half the plane reads -- the kernel
 // took 27 us instead of 18 at 128 images, profiles/proj_sum_ab.txt.)
-static __attribute__((unused)) __global__ __launch_bounds__(64 * kSumMaxSlices) void gemm_nt_sum_bf16x3_kernel(
+__global__ __launch_bounds__(64 * kSumMaxSlices) void gemm_nt_sum_bf16x3_kernel(
     const uint16_t* __restrict__ xs, const uint16_t* __restrict__ w, int M, int N, int K, int kslice, int KS, int m_tiles,
     const uint16_t* __restrict__ bk, const uint16_t* __restrict__ bq, float* __restrict__ kbar, uint16_t* __restrict__ ksp,
     float* __restrict__ cpart, int n_cpart) {
@@ -409,7 +405,7 @@ static __attribute__((unused)) __global__ __launch_bounds__(64 * kSumMaxSlices) 
 // register transpose of gemm_nn_bf16x3_kernel builds the A fragments of the two 32x32 tiles "n = n0 + 2 i' + t": 32 accumulator
 // registers instead of 128, so 4 k-steps of loads fit beside them.  The tile is deposited [slice][n][m] and stored as 256-byte
 // pieces of w's rows.  Requires K % 16 == 0 and N % 8 == 0.
-static __attribute__((unused)) __global__ __launch_bounds__(64 * kSumMaxSlices) void gemm_nn_sum_bf16x3_kernel(
+__global__ __launch_bounds__(64 * kSumMaxSlices) void gemm_nn_sum_bf16x3_kernel(
     const uint16_t* __restrict__ xs, const uint16_t* __restrict__ w, int M, int N, int K, int kslice, int KS, int m_tiles,
     const float* __restrict__ cpart, int n_cpart, float* __restrict__ wout, float* __restrict__ c) {
   __shared__ float slab[kSumMaxSlices][64][33];     // (33: the epilogue reads with n across the lanes)

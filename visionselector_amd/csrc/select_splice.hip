@@ -12,10 +12,8 @@
 //     [qb, qe) it owns: index arrays + row copies from inputs_embeds or from H.  idx (all_indices) is written by slices.
 //   otherwise: topk_select -> splice_index_seg_kernel (one workgroup per prompt, descriptors point into H) -> splice_embed_kernel.
 // Integer arithmetic and raw 16-byte copies only: bit-identical to vsel_lis_select + vsel_splice(_batched) in every output.
-#include "lis_kernels.h"
+#include "lis_stages.h"
 #include "softtopk.h"
-#include "lis_small.h"
-#include "proj_bf16x3.h"
 #include "splice_kernels.h"
 
 namespace vsel {
@@ -75,9 +73,6 @@ static __global__ __launch_bounds__(kSpliceThreads) void splice_index_seg_kernel
     if ((int)nv != g.nvis || (int)nk != g.len_out || (int)nj != g.ko) atomicAdd(&stats[3], 1);
   }
 }
-
-// soft top-k of one row (softtopk.hip)
-int launch_soft_topk_fwd(hipStream_t st, const float* xs, int64_t b, int64_t n, int64_t k, float* ps, float* ts);
 
 // optional extra outputs of the select-splice entries: the soft top-k of the scores the reference's eval forward also publishes
 // (visual.last_combined_scores, EV/token_compression/selector_model.py:190): ps fp32 [sum N], ts fp32 [n_seg]; NULL = not wanted
@@ -371,13 +366,8 @@ static int launch_select_splice(hipStream_t st, const T* h, int d, const vsel_se
               (int)io.total_len, io.visual_id, io.idx, l2p, io.pos, pos_rows, io.mask, io.sel, io.new_ids, io.new_pos, io.new_mask,
               io.src_scratch, io.cu_out, io.stats, (int)l_out);
   VSEL_AFTER_LAUNCH(st, "splice_index_seg_kernel");
-  if (l_out > 0) {
-    const unsigned blocks = (unsigned)std::min<int64_t>(cdiv(l_out, 4), 2048);
-    VSEL_LAUNCH((splice_embed_kernel<T>), dim3(blocks), dim3(256), 0, st, embeds, h, io.src_scratch, (int)l_out, d,
-                       (int)io.total_len, (int)seg->total_rows, new_embeds);
-    VSEL_AFTER_LAUNCH(st, "splice_embed_kernel");
-  }
-  return soft_after();
+  rc = launch_splice_embed(st, std::is_same<T, bf16_t>::value ? VSEL_BF16 : VSEL_F32, embeds, h, io.src_scratch, (int)l_out, d, (int)io.total_len, (int)seg->total_rows, new_embeds);
+  return rc ? rc : soft_after();
 }
 
 }  // namespace vsel
@@ -389,9 +379,8 @@ static int splice_args_check(const void* h, vsel_dtype hdtype, const vsel_segmen
                              const SpliceIO& io, int64_t* l_out) {
   if (!h || !io.ids || !io.embeds || !io.idx || !scores || !io.sel || !io.new_ids || !io.new_embeds || !io.src_scratch || !io.stats)
     return fail(VSEL_ERR_INVALID, "NULL pointer");
-  int rc = check_segments_impl(seg, true);
+  int rc = check_segments(seg, true);
   if (rc) return rc;
-  if (seg->n_seg > 65535) return fail(VSEL_ERR_UNSUPPORTED, "more than 65535 prompts");
   if (seg->n_seg > 1 && (!io.cu_seqlens || !io.cu_out))
     return fail(VSEL_ERR_INVALID, "several prompts need cu_seqlens / cu_seqlens_out");
   if (io.pos_rows < 0 || io.pos_rows > 4 || (io.pos_rows > 0 && (!io.pos || !io.new_pos)))

@@ -172,4 +172,8 @@ __device__ __forceinline__ void soft_topk_row_256x16(const float* __restrict__ x
   else soft_topk_row_256<NWB, 16>(x, n, k, ps, ts, red);
 }
 
+// host launchers of b rows (softtopk.hip), for train.hip and select_splice.hip
+int launch_soft_topk_fwd(hipStream_t st, const float* xs, int64_t b, int64_t n, int64_t k, float* ps, float* ts);
+int launch_soft_topk_bwd(hipStream_t st, const float* g, const float* xs, const float* ts, int64_t b, int64_t n, float* gx);
+
 }  // namespace vsel

@@ -1,7 +1,8 @@
 // Device side of the sequence splice (see splice.hip for the reference lines it replaces): the ordered scan that turns
-// (input_ids, kept visual ranks) into the index arrays of the compressed sequence and a per-row source descriptor, and the
-// row copy that materialises inputs_embeds'.  Shared by splice.hip (vsel_splice, vsel_splice_batched) and select_splice.hip
-// (vsel_lis_select_splice: kept rows are read straight from the token tensor H, never staged in a [k, D] tensor).
+// (input_ids, kept visual ranks) into the index arrays of the compressed sequence and a per-row source descriptor; the
+// row copy that materialises inputs_embeds' is splice.hip's (launch_splice_embed).  Shared by splice.hip (vsel_splice,
+// vsel_splice_batched) and select_splice.hip (vsel_lis_select_splice: kept rows are read straight from the token tensor H,
+// never staged in a [k, D] tensor).
 #pragma once
 #include "common.h"
 
@@ -96,79 +97,8 @@ __device__ __forceinline__ void splice_index_body(
   out_kv = run_kv;
 }
 
-static __attribute__((unused)) __global__ __launch_bounds__(kSpliceThreads) void splice_index_kernel(
-    const int64_t* __restrict__ ids, int L, int64_t visual_id, const int64_t* __restrict__ all_indices, int k, int n_visual,
-    const int64_t* __restrict__ pos, int pos_rows, const int64_t* __restrict__ mask, int64_t* __restrict__ sel,
-    int64_t* __restrict__ new_ids, int64_t* __restrict__ new_pos, int64_t* __restrict__ new_mask,
-    int32_t* __restrict__ src, int32_t* __restrict__ stats, int l_out) {
-  extern __shared__ uint32_t bitmap[];
-  const SpliceSeq sq{0, L, n_visual, 0, k, 0};
-  uint32_t nv, nk, nj;
-  splice_index_body(sq, bitmap, ids, visual_id, all_indices, pos, pos_rows, L, mask, sel, new_ids, new_pos, new_mask, src,
-                    l_out, l_out, nv, nk, nj);
-  if (threadIdx.x == 0) {
-    stats[0] = (int32_t)nv;   // visual tokens found in input_ids (must equal n_visual)
-    stats[1] = (int32_t)nk;   // output length (must equal L')
-    stats[2] = (int32_t)nj;   // kept visual tokens (must equal k)
-  }
-}
-
-// Packed batch: workgroup s splices sequence s.  Output offsets need no scan: sequence s starts at
-// cu_seqlens[s] - cu_visual[s] + cu_kept[s].  stats (zeroed by the host wrapper) accumulate with integer atomics.
-static __attribute__((unused)) __global__ __launch_bounds__(kSpliceThreads) void splice_index_batched_kernel(
-    const int64_t* __restrict__ ids, const int32_t* __restrict__ cu_seqlens, const int32_t* __restrict__ cu_visual,
-    const int32_t* __restrict__ cu_kept, int n_seq, int max_visual, int64_t visual_id, const int64_t* __restrict__ all_indices,
-    const int64_t* __restrict__ pos, int pos_rows, int total_in, int64_t* __restrict__ sel, int64_t* __restrict__ new_ids,
-    int64_t* __restrict__ new_pos, int32_t* __restrict__ src, int32_t* __restrict__ cu_out, int32_t* __restrict__ stats,
-    int l_out) {
-  extern __shared__ uint32_t bitmap[];
-  const int s = blockIdx.x;
-  SpliceSeq sq;
-  sq.p0 = cu_seqlens[s];
-  sq.L = cu_seqlens[s + 1] - sq.p0;
-  sq.nvis = cu_visual[s + 1] - cu_visual[s];
-  sq.j0 = cu_kept[s];
-  sq.k = cu_kept[s + 1] - sq.j0;
-  sq.q0 = sq.p0 - cu_visual[s] + sq.j0;
-  const int len_out = sq.L - sq.nvis + sq.k;
-  const bool sane = sq.L >= 0 && sq.nvis >= 0 && sq.nvis <= max_visual && sq.nvis <= sq.L && sq.k >= 0 && sq.k <= sq.nvis &&
-                    sq.p0 >= 0 && sq.p0 + sq.L <= total_in && sq.q0 >= 0 && sq.q0 + len_out <= l_out;
-  if (threadIdx.x == 0) {
-    cu_out[s] = sq.q0;
-    if (s == n_seq - 1) cu_out[n_seq] = sq.q0 + len_out;
-  }
-  if (!sane) {                       // uniform per workgroup: descriptors that disagree are reported, nothing is written
-    if (threadIdx.x == 0) atomicAdd(&stats[3], 1);
-    return;
-  }
-  uint32_t nv, nk, nj;
-  splice_index_body(sq, bitmap, ids, visual_id, all_indices, pos, pos_rows, total_in, nullptr, sel, new_ids, new_pos, nullptr,
-                    src, l_out, sq.q0 + len_out, nv, nk, nj);
-  if (threadIdx.x == 0) {
-    atomicAdd(&stats[0], (int32_t)nv);
-    atomicAdd(&stats[1], (int32_t)nk);
-    atomicAdd(&stats[2], (int32_t)nj);
-    if ((int)nv != sq.nvis || (int)nk != len_out || (int)nj != sq.k) atomicAdd(&stats[3], 1);
-  }
-}
-
-// n_rows / n_vis bound the two source tensors: a descriptor outside them (a splice whose token counts disagree with
-// input_ids, reported through stats) yields a zero row instead of an out-of-bounds read.
-template <typename T>
-__global__ __launch_bounds__(256) void splice_embed_kernel(const T* __restrict__ embeds, const T* __restrict__ vis,
-                                                           const int32_t* __restrict__ src, int l_out, int d, int n_rows,
-                                                           int n_vis, T* __restrict__ out) {
-  constexpr int V = Elem<T>::kVec;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int q = blockIdx.x * 4 + wave; q < l_out; q += gridDim.x * 4) {
-    const int s = src[q];
-    const bool ok = s >= 0 ? s < n_rows : (-(int64_t)s - 1) < n_vis;
-    const T* from = s >= 0 ? embeds + (int64_t)s * d : vis + (int64_t)(-s - 1) * d;
-    const u32x4* sp = reinterpret_cast<const u32x4*>(from);
-    u32x4* dp = reinterpret_cast<u32x4*>(out + (int64_t)q * d);
-    const u32x4 zero = {0u, 0u, 0u, 0u};
-    for (int v = lane; v < d / V; v += 64) dp[v] = ok ? sp[v] : zero;
-  }
-}
+// The row copy after every index scan (splice.hip): out[q] = embeds[src[q]] or vis[-src[q] - 1], rows of `dtype`; none for l_out <= 0
+int launch_splice_embed(hipStream_t st, vsel_dtype dtype, const void* embeds, const void* vis, const int32_t* src, int l_out, int d,
+                        int n_rows, int n_vis, void* out);
 
 }  // namespace vsel

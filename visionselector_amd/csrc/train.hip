@@ -1,7 +1,7 @@
 // Training LIS block (reference: qwen-vl-finetune/compression_method/selector_model.py:158-173 forward,
 // :308-311 constraint loss, :60-70 TopK.backward; llava-ov-15/compression_method/selector_model.py:127-142).
 //
-// forward : scores (lis_kernels.h) -> soft top-k (the root of _find_ts by bracketed Newton steps, softtopk.h) -> h_new = ps * h -> hard mask y -> BCE
+// forward : scores (lis_scores_stage, lis_stages.h) -> soft top-k (the root of _find_ts by bracketed Newton steps, softtopk.h) -> h_new = ps * h -> hard mask y -> BCE
 // backward: closed form of autograd through the scorer (SURVEY.md section 7 hard part 4).  With g = dL/dscores,
 //           rs = 1/sqrt(Hd), xbar = mean x, kbar = Wk xbar + bk:
 //             dWq = (kbar rs) (x) sum_i g_i x_i        dbq = kbar rs sum_i g_i
@@ -9,14 +9,10 @@
 //             dWk = dk (x) sum_i x_i                   dbk = N dk
 //             dx_i = ps_i dh'_i + g_i rs Wq^T kbar + Wk^T dk
 //           i.e. two more sweeps over the token tensor (row dots, weighted column sums) + GEMVs + rank-1 writes.
-#include "lis_kernels.h"
-#include "lis_small.h"
+#include "lis_stages.h"
 #include "softtopk.h"
 
 namespace vsel {
-
-int launch_soft_topk_fwd(hipStream_t st, const float* xs, int64_t b, int64_t n, int64_t k, float* ps, float* ts);
-int launch_soft_topk_bwd(hipStream_t st, const float* g, const float* xs, const float* ts, int64_t b, int64_t n, float* gx);
 
 // h_new[i, :] = (ps[i] * h[i, :]).type(dtype)     (:164-166)   wave per row
 // BCE: one EXTRA workgroup (the last) computes the constraint loss of the row instead of rows of h_new -- bce = mean_i
@@ -783,7 +779,6 @@ static int scores_bwd_impl(hipStream_t st, const float* g, const T* h, int64_t n
                            const TrainPlan& tp, float* dwq, float* dbq, float* dwk, float* dbk, T* dh, const T* dhn,
                            const float* ps, float* factors = nullptr, const float* fuse_dps = nullptr,
                            const float* fuse_scores = nullptr, const float* fuse_ts = nullptr) {
-  constexpr int V = Elem<T>::kVec;
   const int d = (int)sc->d, hd = (int)sc->hd;
   const LisPlan& p = tp.lis;
   float* wpart = (float*)(ws + tp.off_wpart);
@@ -815,9 +810,9 @@ static int scores_bwd_impl(hipStream_t st, const float* g, const T* h, int64_t n
     if constexpr (std::is_same<TW, bf16_t>::value) {
       float* gbuf = (float*)(ws + tp.off_g);
       if (int rc = launch_wcolsum<T, true>(st, h, fuse_dps, (int)n, d, tp.wsplits, wpart, fuse_scores, fuse_ts, gbuf)) return rc;
-      VSEL_LAUNCH(proj_nt_small_pair_kernel, dim3((unsigned)cdiv(hd, 32), p.ks1, 2), dim3(64), 0, st, wpart, wpart + d, make_view(&seg1), 1,
-                  tp.wsplits, (const uint16_t*)sc->wk, (const uint16_t*)sc->wq, hd, d, p.kslice1, part1, dkraw, (int64_t)2 * d, 1, 0);
-      VSEL_AFTER_LAUNCH(st, "proj_nt_small_pair_kernel");
+      if (int rc = launch_proj_nt_small_pair(st, wpart, wpart + d, make_view(&seg1), 1, tp.wsplits, (const uint16_t*)sc->wk, (const uint16_t*)sc->wq,
+                                             hd, d, p.kslice1, p.ks1, part1, dkraw, (int64_t)2 * d, 1, 0))
+        return rc;
       if (!factors && hd <= 64 * kOuterRowGroups) {
         VSEL_LAUNCH((outer_finish_pair_kernel<TW>), dim3((unsigned)cdiv(d, 1024), kOuterRowGroups, 2), dim3(256), 0, st, wpart, gbuf, (int)n, d,
                     tp.wsplits, part1, dkraw, p.ks1, hd, (const TW*)sc->bk, (const TW*)sc->bq, rs, xsum, gx, xbar, sg, kbar, dk, a, dbq, dbk,
@@ -843,28 +838,13 @@ static int scores_bwd_impl(hipStream_t st, const float* g, const T* h, int64_t n
   VSEL_AFTER_LAUNCH(st, "wcolsum_finish_kernel");
   // kbar = Wk xbar + bk.  bf16 weights: the forward's single-wave-per-tile bf16x3 kernel, its prologue summing the row splits
   // of wpart itself (same bits as the forward's kbar); else the fp32-input MFMA form
-  if (small) {
-    VSEL_LAUNCH(proj_nt_small_kernel, dim3((unsigned)cdiv(hd, 32), p.ks1), dim3(64), 0, st, wpart, make_view(&seg1), 1,
-                       tp.wsplits, (const uint16_t*)sc->wk, hd, d, p.kslice1, part1, (int64_t)2 * d, 1);
-    VSEL_AFTER_LAUNCH(st, "proj_nt_small_kernel");
-  } else {
-    VSEL_LAUNCH((gemm_nt_kernel<TW>), dim3((unsigned)cdiv(hd, 32), 1, p.ks1), dim3(64), 0, st, xbar, (const TW*)sc->wk, 1,
-                       hd, d, p.kslice1, part1);
-    VSEL_AFTER_LAUNCH(st, "gemm_nt_kernel");
-  }
-  VSEL_LAUNCH((kbar_finish_kernel<TW>), dim3(1), dim3(256), 0, st, part1, p.ks1, 1, hd, (const TW*)sc->bk,
-                     (const TW*)sc->bq, kbar, c);
-  VSEL_AFTER_LAUNCH(st, "kbar_finish_kernel");
+  int rc = small ? launch_proj_nt_small(st, wpart, make_view(&seg1), 1, tp.wsplits, (const uint16_t*)sc->wk, hd, d, p.kslice1, p.ks1, part1, (int64_t)2 * d, 1)
+                 : launch_gemm_nt(st, sc->wdtype, xbar, sc->wk, 1, hd, d, p.kslice1, p.ks1, part1);
+  if (rc || (rc = launch_kbar_finish(st, sc->wdtype, part1, p.ks1, 1, hd, sc->bk, sc->bq, kbar, c))) return rc;
   // dk = (Wq gx + bq sg) rs / N
-  if (small) {
-    VSEL_LAUNCH(proj_nt_small_kernel, dim3((unsigned)cdiv(hd, 32), p.ks1), dim3(64), 0, st, wpart + d, make_view(&seg1), 1,
-                       tp.wsplits, (const uint16_t*)sc->wq, hd, d, p.kslice1, dkraw, (int64_t)2 * d, 0);
-    VSEL_AFTER_LAUNCH(st, "proj_nt_small_kernel");
-  } else {
-    VSEL_LAUNCH((gemm_nt_kernel<TW>), dim3((unsigned)cdiv(hd, 32), 1, p.ks1), dim3(64), 0, st, gx, (const TW*)sc->wq, 1,
-                       hd, d, p.kslice1, dkraw);
-    VSEL_AFTER_LAUNCH(st, "gemm_nt_kernel");
-  }
+  rc = small ? launch_proj_nt_small(st, wpart + d, make_view(&seg1), 1, tp.wsplits, (const uint16_t*)sc->wq, hd, d, p.kslice1, p.ks1, dkraw, (int64_t)2 * d, 0)
+             : launch_gemm_nt(st, sc->wdtype, gx, sc->wq, 1, hd, d, p.kslice1, p.ks1, dkraw);
+  if (rc) return rc;
   VSEL_LAUNCH((dk_finish_kernel<TW>), dim3((unsigned)cdiv(hd, 256)), dim3(256), 0, st, dkraw, p.ks1, hd,
                      (const TW*)sc->bq, kbar, sg, rs, (int)n, dk, a, dbq, dbk);
   VSEL_AFTER_LAUNCH(st, "dk_finish_kernel");
@@ -875,16 +855,9 @@ static int scores_bwd_impl(hipStream_t st, const float* g, const T* h, int64_t n
   }
   }
   if (dh) {
-    VSEL_LAUNCH((gemm_nn_kernel<TW>), dim3((unsigned)cdiv(d, 256), 1, p.ks2), dim3(64), 0, st, kbar, (const TW*)sc->wq, 1,
-                       d, hd, p.kslice2, part2);
-    VSEL_AFTER_LAUNCH(st, "gemm_nn_kernel");
-    VSEL_LAUNCH(slice_sum_kernel, dim3((unsigned)cdiv(d, 256)), dim3(256), 0, st, part2, p.ks2, (int64_t)d, w);
-    VSEL_AFTER_LAUNCH(st, "slice_sum_kernel");
-    VSEL_LAUNCH((gemm_nn_kernel<TW>), dim3((unsigned)cdiv(d, 256), 1, p.ks2), dim3(64), 0, st, dk, (const TW*)sc->wk, 1, d,
-                       hd, p.kslice2, part2);
-    VSEL_AFTER_LAUNCH(st, "gemm_nn_kernel");
-    VSEL_LAUNCH(slice_sum_kernel, dim3((unsigned)cdiv(d, 256)), dim3(256), 0, st, part2, p.ks2, (int64_t)d, u);
-    VSEL_AFTER_LAUNCH(st, "slice_sum_kernel");
+    // w = Wq^T kbar, u = Wk^T dk
+    if (int rc = launch_gemm_nn(st, sc->wdtype, kbar, sc->wq, 1, d, hd, p.kslice2, p.ks2, part2, w)) return rc;
+    if (int rc = launch_gemm_nn(st, sc->wdtype, dk, sc->wk, 1, d, hd, p.kslice2, p.ks2, part2, u)) return rc;
     VSEL_LAUNCH((dh_kernel<T>), dim3(row_blocks), dim3(256), 0, st, dhn, ps, g, w, u, rs, (int)n, d, dh);
     VSEL_AFTER_LAUNCH(st, "dh_kernel");
   }
